@@ -6,13 +6,19 @@ resident in HBM, x [16, 30, 3, 224, 224] per GPU.  BASELINE.json's metric is "cl
 fwd+bwd", so the timed step is the TRAIN step of the reference (src/trainer.py:108-177):
 frozen-encoder forward + decoder forward + decoder backward + SGD(momentum 0.95) step
 (BASELINE configs[2] at N = 1; the encoder has no backward in the reference).  `--mode infer`
-times configs[1] instead (forward-only `Detector.predict`, the inference.py path); the default
+times configs[1] instead (forward-only `Detector.predict`, the inference.py path); a `--full`
 run reports it as `forward_only` next to the headline.  With --gpus N the driver launches one
 rank per GPU (torch.distributed, backend nccl = RCCL); clips are independent, so ranks shard
 them: the only collectives are the gradient all-reduce of the decoder parameters (train) and
 the all-gather of per-clip logits (infer); scaling is weak (16 clips per GPU).
 
-Prints ONE JSON line on rank 0 with the whole-job clips/s plus
+A plain run sets up, warms up, times exactly --steps steps and prints ONE JSON line on rank 0 with the
+whole-job clips/s (`value`), `ms_per_step` and the host figures below.  `--dump-outputs DIR` then also writes what
+the last timed step computed as DIR/<name>.npy (float32; see `dump_outputs`); the inputs and weights are seeded, so
+two builds run with the same arguments can be compared array by array.  `--full` adds what the headline does not need:
+  forward_only — with --mode train, BASELINE configs[1] timed after the headline;
+  secondary    — single GPU, ViT-B/16 bf16 train: the ViT-L/14 bf16 / fp8 forward lines and the adapter train line
+                 (`secondary_configs`; --no-secondary skips them);
   roofline     — the dominant kernel (the MLP c_fc GEMM, M x 3072 x 768 with QuickGELU epilogue):
                  algorithmic FLOPs per launch / its average launch duration measured with HIP
                  events on the launch stream during the timed steps, against the 2.5 PFLOP/s
@@ -21,7 +27,7 @@ Prints ONE JSON line on rank 0 with the whole-job clips/s plus
                  launch its kernels one by one so that these launches can be bracketed — same kernels,
                  same stream, inside the timed region);
   cpu_baseline — the CPU oracle (this repo's PyTorch-CPU port of the reference path) timed on
-                 this host on a bounded sample (one 30-frame clip), rank 0, N=1 only.
+                 this host on a bounded sample (one 30-frame clip), rank 0, N=1 only (--no-cpu-baseline skips it).
 Host figures: `host_enqueue_ms_each_step` is the wall time the host spent inside each timed step's calls,
 `host_enqueue_ms_median` their median, `host_enqueue_ms_per_step` their mean over the steps in which the host did not
 block, `host_queue_stall_ms_total` the time of those in which it did, and `host_cpu_ms_per_step` the CPU seconds of all
@@ -64,9 +70,11 @@ if __name__ == "__main__" and "--gpus" in " ".join(sys.argv[1:]):
 
 import torch  # noqa: E402
 
-PEAK_BF16_TFLOPS = 2500.0  # dense, /opt/skills/guides/MI355X_MICROARCH.md chip table
+PEAK_BF16_TFLOPS = 2500.0  # dense, MI355X chip specification
 PEAK_F32_TFLOPS = 157.3
-PEAK_FP8_TFLOPS = 5000.0   # dense, block-scaled e4m3 (same table)
+PEAK_FP8_TFLOPS = 5000.0   # dense, block-scaled e4m3 (same specification)
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs writes at most this much
+DUMP_SAMPLE = 65536           # elements kept of a larger tensor (a fixed, seeded choice of positions)
 
 
 def parse():
@@ -81,12 +89,18 @@ def parse():
                     help="fp8 = BASELINE configs[4]: e4m3 operands for the encoder's q|k|v, c_fc and c_proj GEMMs (use with --arch ViT-L/14)")
     ap.add_argument("--frame-chunk", type=int, default=-1, help="frames per encoder pass (-1 = package default)")
     ap.add_argument("--streams", type=int, default=-1, help="HIP streams for independent frame chunks (-1 = package default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the dominant kernel's roofline (the last three timed steps "
+                         "launch the encoder kernel by kernel), the forward-only leg, the secondary lines and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--kv-export", action="store_true",
                     help="A/B: let the projection's epilogue export K/V + positional embedding (round 1's hand-over) instead of the "
                          "decoder reading them in place")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the informational ViT-L/14 lines (BASELINE configs[3] bf16 / configs[4] fp8) of the default single-GPU run")
+                    help="with --full: skip the informational ViT-L/14 lines (BASELINE configs[3] bf16 / configs[4] fp8) and the adapter "
+                         "line of the single-GPU run")
     ap.add_argument("--mode", default="train", choices=["train", "infer"])
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL over xGMI; the default) or gloo (rehearsal on one GPU)")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal only: every rank uses cuda:0")
@@ -265,6 +279,43 @@ def cpu_baseline(cfg, sd, args):
                       f"torch {torch.__version__} CPU threads={cores}"}
 
 
+def dump_outputs(out_dir, det, out, mode):
+    """`--dump-outputs`: what a caller of the timed step holds after the last one, as float32 DIR/<name>.npy.
+    Both modes: `task<i>_logits` [B, out_dim] of rank 0's clips.  Train adds `task<i>_loss` (the loss the step
+    backpropagated) and, per trainable parameter, `param.<name>` (its value after the optimizer step) and `grad.<name>`
+    (the gradient that step applied).  A tensor of more than DUMP_SAMPLE elements is written as DUMP_SAMPLE of its
+    flattened elements, at positions drawn from a generator seeded with 0 and sorted: the same positions in every run."""
+    import numpy as np
+    arrays = {}
+    if mode == "train":
+        task_losses, task_logits = out
+        for i, loss in enumerate(task_losses):
+            if torch.is_tensor(loss):
+                arrays[f"task{i}_loss"] = loss
+        for name, p in det.named_parameters():
+            if p.requires_grad:
+                arrays[f"param.{name}"] = p
+                if p.grad is not None:
+                    arrays[f"grad.{name}"] = p.grad
+    else:
+        task_logits = out
+    for i, logits in enumerate(task_logits):
+        arrays[f"task{i}_logits"] = logits
+    total = sum(min(t.numel(), DUMP_SAMPLE) * 4 for t in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_BUDGET_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    positions = {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > DUMP_SAMPLE:
+            if a.size not in positions:
+                positions[a.size] = np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))
+            a = a.reshape(-1)[positions[a.size]]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    print(f"bench.py: wrote {len(arrays)} arrays ({total / 2**20:.1f} MiB) to {out_dir}", file=sys.stderr, flush=True)
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -342,10 +393,11 @@ def main():
 
     def train_step():
         det.zero_grad(set_to_none=True)
-        task_losses, _, other = det(x, [y], m, train=True, single_task=0)
+        task_losses, task_logits, other = det(x, [y], m, train=True, single_task=0)
         (task_losses[0].mean() + sum(other.values())).backward()
         ddist.allreduce_gradients(trainable)  # RCCL over xGMI: one flat all-reduce of the decoder gradients
         opt.step()
+        return task_losses, task_logits
 
     def barrier():
         if dist is not None:
@@ -367,12 +419,16 @@ def main():
         t0 = time.perf_counter()
         c0 = time.process_time()
         per_step = []
+        out = None
         for i in range(steps):
             if prof_steps and i == steps - prof_steps:
                 det.encoder_graph_pause = True
                 capi.profile_gemm(epilogue=capi.EPI_BIAS_QUICKGELU)
             ts = time.perf_counter()
-            fn()
+            if i == steps - 1:
+                out = fn()  # only the last step's results outlive it (--dump-outputs)
+            else:
+                fn()
             per_step.append((time.perf_counter() - ts) * 1e3)
         det.encoder_graph_pause = False
         host_steps[:] = per_step
@@ -387,7 +443,7 @@ def main():
             tt = torch.tensor([dt], device=device, dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = tt.item()
-        return dt, spans
+        return dt, spans, out
 
     if args.precision == "fp8":  # static activation scales from the synthetic batch itself, before anything is timed
         det.calibrate_fp8(x[:2])
@@ -416,7 +472,10 @@ def main():
             graph_note = f"HIP graphs switched off: {slow.item() * 1e3:.0f} ms/step with graphs at world {world}"
             for _ in range(2):
                 step()
-    dt, spans = timed(step, args.steps, True)
+    dt, spans, out = timed(step, args.steps, args.full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, det, out, args.mode)
+    del out
     host_enqueue_ms, host_cpu_ms = host_ms
     host_step_ms = [round(v, 2) for v in host_steps]
     # a step in which the host blocked on the runtime's queue depth (it runs many graph-replay steps ahead of the GPU) is not
@@ -428,35 +487,14 @@ def main():
         host_enqueue_ms = sum(worked) / len(worked)
     host_stall_ms = sum(stalled)
     fwd_only = None
-    if args.mode == "train":  # informational: BASELINE configs[1], forward-only, outside the headline's timed region
+    if args.full and args.mode == "train":  # informational: BASELINE configs[1], forward-only, outside the headline's timed region
         det.eval()
         for _ in range(PRIME_STEPS):
             infer_step()
-        dt_i, _ = timed(infer_step, max(2, args.steps // 2), False)
+        dt_i, _, _ = timed(infer_step, max(2, args.steps // 2), False)
         fwd_only = world * B * max(2, args.steps // 2) / dt_i
 
     if rank == 0:
-        # roofline of the dominant kernel: algorithmic FLOPs of its launches / the time the kernel was running.
-        # Frame chunks run on two streams, so launches can overlap each other and other kernels: the
-        # denominator is the UNION of the launches' HIP-event intervals (a lower bound on the kernel's rate).
-        busy, cur_s, cur_e = 0.0, None, None
-        for st_ms, en_ms, _ in sorted(spans):
-            if cur_e is None or st_ms > cur_e:
-                busy += (cur_e - cur_s) if cur_e is not None else 0.0
-                cur_s, cur_e = st_ms, en_ms
-            else:
-                cur_e = max(cur_e, en_ms)
-        busy += (cur_e - cur_s) if cur_e is not None else 0.0
-        avg_ms = busy / max(1, len(spans))
-        achieved = sum(fl for _, _, fl in spans) / (busy * 1e-3) / 1e12 if spans else None
-        launch_m = int(round(spans[0][2] / (2.0 * 4 * width * width))) if spans else M
-        peak = {"bf16": PEAK_BF16_TFLOPS, "fp32": PEAK_F32_TFLOPS, "fp8": PEAK_FP8_TFLOPS}[args.precision]
-        traffic = None
-        tpath = os.path.join(ROOT, "profiles", "dominant_kernel_traffic.json")
-        if os.path.exists(tpath):  # PMC-measured HBM bytes per launch; only valid for the shape it was measured on
-            tj = json.load(open(tpath))
-            if tj.get("shape") == {"M": launch_m, "N": 4 * width, "K": width}:
-                traffic = tj.get("hbm_bytes_per_launch")
         line = {
             "metric": f"1-sec clips/sec (30x224x224 frames) {args.arch}", "value": round(world * B * args.steps / dt, 3),
             "unit": "clips/s", "n_gpus": world, "ranks_seen": ranks_seen, "steps": args.steps, "warmup": args.warmup,
@@ -471,23 +509,45 @@ def main():
                                      f"random-init weights, inputs resident in HBM",
                        "mode": args.mode, "adapter": args.adapter, "clips_per_gpu": B, "frames_per_clip": T, "hip_graphs": bool(det.static_graphs) and not det.decoder._graphs_failed and not (det.adapter is not None and det.adapter._graphs_failed), "encoder_graph": bool(det._enc_graphs) and not det._enc_graphs_failed, "pipelined_encoder": bool(det.pipeline_encoder), "frame_chunk": det.encoder.frame_chunk,
                        "streams": det.encoder.streams},
-            "roofline": {"bound": "mfma", "kernel": "c_fc GEMM + QuickGELU (M=%d, N=%d, K=%d)" % (launch_m, 4 * width, width),
-                         "achieved": round(achieved, 2) if achieved else None, "peak": peak, "unit": "TFLOP/s",
-                         "frac": round(achieved / peak, 4) if achieved else None, "traffic": traffic,
-                         "launches_timed": len(spans), "avg_launch_ms": round(avg_ms, 4)},
         }
+        if args.full:
+            # roofline of the dominant kernel: algorithmic FLOPs of its launches / the time the kernel was running.
+            # Frame chunks run on two streams, so launches can overlap each other and other kernels: the
+            # denominator is the UNION of the launches' HIP-event intervals (a lower bound on the kernel's rate).
+            busy, cur_s, cur_e = 0.0, None, None
+            for st_ms, en_ms, _ in sorted(spans):
+                if cur_e is None or st_ms > cur_e:
+                    busy += (cur_e - cur_s) if cur_e is not None else 0.0
+                    cur_s, cur_e = st_ms, en_ms
+                else:
+                    cur_e = max(cur_e, en_ms)
+            busy += (cur_e - cur_s) if cur_e is not None else 0.0
+            avg_ms = busy / max(1, len(spans))
+            achieved = sum(fl for _, _, fl in spans) / (busy * 1e-3) / 1e12 if spans else None
+            launch_m = int(round(spans[0][2] / (2.0 * 4 * width * width))) if spans else M
+            peak = {"bf16": PEAK_BF16_TFLOPS, "fp32": PEAK_F32_TFLOPS, "fp8": PEAK_FP8_TFLOPS}[args.precision]
+            traffic = None
+            tpath = os.path.join(ROOT, "profiles", "dominant_kernel_traffic.json")
+            if os.path.exists(tpath):  # PMC-measured HBM bytes per launch; only valid for the shape it was measured on
+                tj = json.load(open(tpath))
+                if tj.get("shape") == {"M": launch_m, "N": 4 * width, "K": width}:
+                    traffic = tj.get("hbm_bytes_per_launch")
+            line["roofline"] = {"bound": "mfma", "kernel": "c_fc GEMM + QuickGELU (M=%d, N=%d, K=%d)" % (launch_m, 4 * width, width),
+                                "achieved": round(achieved, 2) if achieved else None, "peak": peak, "unit": "TFLOP/s",
+                                "frac": round(achieved / peak, 4) if achieved else None, "traffic": traffic,
+                                "launches_timed": len(spans), "avg_launch_ms": round(avg_ms, 4)}
         if det.decoder._graphs_failed and not graph_note:
             graph_note = "HIP graph capture refused by the runtime, decoder on eager launches: " + det.decoder._graphs_failed[:160]
         if graph_note:
             line["config"]["note"] = graph_note
         if fwd_only is not None:
             line["forward_only"] = {"value": round(fwd_only, 3), "unit": "clips/s", "workload": "BASELINE configs[1]: Detector.predict"}
-        if world == 1 and not args.no_secondary and args.arch == "ViT-B/16" and args.precision == "bf16" and args.mode == "train":
+        if args.full and world == 1 and not args.no_secondary and args.arch == "ViT-B/16" and args.precision == "bf16" and args.mode == "train":
             try:  # informational: a failure here must not cost the headline line
                 line["secondary"] = secondary_configs(args, device)
             except Exception as e:  # noqa: BLE001
                 line["secondary"] = [{"error": f"{type(e).__name__}: {e}"[:300]}]
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(cfg, sd, args)
             except Exception as e:  # noqa: BLE001

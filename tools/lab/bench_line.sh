@@ -1,3 +1,3 @@
 #!/bin/bash
-# one summary line of a bench run: tools/lab/bench_line.sh [bench.py flags]
-python bench.py "$@" 2>/dev/null | tail -1 > /tmp/bench_line.json && python tools/lab/show_bench.py /tmp/bench_line.json
+# one summary line of a full bench run (roofline, forward-only and secondary lines included): tools/lab/bench_line.sh [bench.py flags]
+out=$(mktemp) && python bench.py --full "$@" 2>/dev/null | tail -1 > "$out" && python tools/lab/show_bench.py "$out"; rc=$?; rm -f "$out"; exit $rc
