@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libdfdclip_hip.so")
 
 F32, BF16 = 0, 1
 EPI_BIAS, EPI_BIAS_QUICKGELU, EPI_BIAS_RESIDUAL, EPI_PATCH_EMBED, EPI_QKV_EXPORT, EPI_RESIDUAL_POS = range(6)
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 _DTYPE = {torch.float32: F32, torch.bfloat16: BF16}
 FP8 = 2           # ABI code of OCP e4m3; stored in uint8 / torch.float8_e4m3fn tensors
@@ -112,6 +112,11 @@ SIGNATURES = {
                              c_void_p]),
     "dfd_head_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                              c_int, c_float, POINTER(DropoutDesc), c_void_p]),
+    "dfd_compinv_loss_workspace": (c_size_t, [c_int, c_int]),
+    "dfd_compinv_loss_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p]),
+    "dfd_compinv_loss_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None
@@ -565,3 +570,39 @@ def head_bwd(raw, dlogits, proj, feat, dfeat_ext, dz, dfeat, dproj):
     _check(load_library().dfd_head_bwd(_ptr(raw), _ptr(dlogits), _ptr(proj), _ptr(feat), _ptr(dfeat_ext), _ptr(dz), _ptr(dfeat),
                                        _ptr(dproj), B, D, od, _stream()), "dfd_head_bwd")
     return dfeat
+
+
+# ---- CompInvEncoder pair loss ------------------------------------------------------------------
+
+def compinv_loss_workspace_bytes(P, D):
+    return int(load_library().dfd_compinv_loss_workspace(int(P), int(D)))
+
+
+def _compinv_check(k, v, B, T, P, L):
+    assert k.dtype == v.dtype and k.shape == v.shape and k.is_contiguous() and v.is_contiguous()
+    assert k.dim() == 3 and k.shape[0] == L and k.shape[1] == B * T * P, (tuple(k.shape), B, T, P, L)
+
+
+def compinv_loss_fwd(k, v, B, T, P, workspace, match, norm, recon=None):
+    """k, v [L, B*T*P, D] (the adapted K/V) -> workspace[:P*D] = M, match = ||M|| / P, norm = ||M||, recon = 0
+    (device f32 scalars; nothing is read back)."""
+    _dev(k, v, workspace, match, norm, recon)
+    L, _, D = k.shape
+    _compinv_check(k, v, B, T, P, L)
+    assert workspace.dtype == torch.float32 and workspace.numel() * 4 >= compinv_loss_workspace_bytes(P, D)
+    assert match.dtype == norm.dtype == torch.float32 and (recon is None or recon.dtype == torch.float32)
+    _check(load_library().dfd_compinv_loss_fwd(_ptr(k), _ptr(v), _DTYPE[k.dtype], B, T, P, D, L, _ptr(workspace), _ptr(match),
+                                               _ptr(norm), _ptr(recon), _stream()), "dfd_compinv_loss_fwd")
+    return match
+
+
+def compinv_loss_bwd(k, v, B, T, P, workspace, norm, grad, dk, dv):
+    """dk, dv (dtype and layout of k, v) = d match / d (k, v) scaled by the device scalar `grad`."""
+    _dev(k, v, workspace, norm, grad, dk, dv)
+    L, _, D = k.shape
+    _compinv_check(k, v, B, T, P, L)
+    assert dk.dtype == dv.dtype == k.dtype and dk.shape == dv.shape == k.shape and dk.is_contiguous() and dv.is_contiguous()
+    assert grad.dtype == norm.dtype == torch.float32 and grad.numel() == 1 and norm.numel() == 1
+    _check(load_library().dfd_compinv_loss_bwd(_ptr(k), _ptr(v), _DTYPE[k.dtype], B, T, P, D, L, _ptr(workspace), _ptr(norm),
+                                               _ptr(grad), _ptr(dk), _ptr(dv), _stream()), "dfd_compinv_loss_bwd")
+    return dk, dv

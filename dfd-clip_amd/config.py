@@ -56,3 +56,17 @@ def default_detector_config():
     C.weight_decay = 0.01
     C.optimizer = "sgd"
     return C
+
+
+def default_compinv_config():
+    """Same keys and defaults as `CompInvEncoder.get_default_config` (reference `src/models.py:955-966`)."""
+    C = ConfigNode()
+    C.name = "CompInvEncoder"
+    C.architecture = "ViT-B/16"
+    C.decode_mode = "stride"
+    C.decode_stride = 2
+    C.decode_indices = []
+    C.adapter = ConfigNode()
+    C.dropout = 0.0
+    C.mode = 0
+    return C

@@ -15,6 +15,10 @@ code, so that a reference user finds the same step semantics on top of `Detector
   evaluate        `Evaluator.run` (`src/evaluator.py:50-97`) + the metric callbacks
                   (`src/callbacks/metrics.py:86-155`): no_grad, eval(), model(x, y_list, m, single_task)
                   -> softmax -> gather over ranks -> accuracy / AUROC on p[:, 1].
+  compinv_train_step / compinv_evaluate
+                  `CompInvTrainer.run` / `CompInvEvaluator.run` (`src/trainer.py:263-303`, `src/evaluator.py:138-172`):
+                  the adapter pre-training step (forward -> backward(recon + match) per batch, one optimizer
+                  step) and its no_grad evaluation pass.
   infer_videos    `inference.py:105-162`: per video, chunks of `batch_size` clips -> predict -> softmax ->
                   clip- or video-level (mean over clips) probabilities -> gather -> accuracy / AUROC with
                   the dummy [0, 1] pair the reference appends before computing.
@@ -98,6 +102,37 @@ def train_step(model, optimizer, batches, scheduler=None, total_tasks=None, teac
     model.zero_grad()
     if teacher is not None:
         teacher.update(model)
+    return out
+
+
+def compinv_train_step(model, optimizer, batches, scheduler=None):
+    """One `CompInvTrainer` step for a `CompInvEncoder`: `batches` = list of (frames, comp), one per training set.
+    Returns {"recon": [...], "match": [...]}, detached 0-dim device tensors per batch."""
+    model.zero_grad()
+    model.train()
+    out = {"recon": [], "match": []}
+    for frames, comp in batches:
+        recon, match = model(frames, comp)
+        (recon + match).backward()
+        out["recon"].append(recon.detach())
+        out["match"].append(match.detach())
+    ddist.allreduce_gradients([p for p in model.parameters() if p.requires_grad])
+    optimizer.step()
+    if scheduler is not None:
+        step_scheduler(scheduler)
+    model.zero_grad()
+    return out
+
+
+@torch.no_grad()
+def compinv_evaluate(model, batches):
+    """`CompInvEvaluator.run`: eval(), no_grad, model(frames, comp) per batch -> {"recon": [...], "match": [...]}."""
+    model.eval()
+    out = {"recon": [], "match": []}
+    for frames, comp in batches:
+        recon, match = model(frames, comp)
+        out["recon"].append(recon)
+        out["match"].append(match)
     return out
 
 

@@ -190,6 +190,21 @@ def random_state_dict(config, num_frames, seed=0):
     return sd
 
 
+def random_compinv_state_dict(config, seed=0):
+    """Seeded fp32 `CompInvEncoder` state_dict (reference key names): `encoder.*` as in `random_state_dict`, then
+    `adapter.l{i}_{k|v}.*` for the tapped layers."""
+    arch = config.architecture
+    layers = ARCHS[arch][3]
+    rng = np.random.default_rng(seed)
+    sd = OrderedDict()
+    for k, shp in encoder_schema(arch).items():
+        sd["encoder." + k] = _fill(rng, k, shp)
+    st = config.adapter.struct
+    for k, shp in adapter_schema(arch, len(resolve_layer_indices(config, layers)), st.type, int(st.x)).items():
+        sd["adapter." + k] = _fill(rng, k, shp)
+    return sd
+
+
 def synthetic_clips(b, t, res, seed=1234, masked_tail=True):
     """Synthetic post-`Normalize` frames and padding mask (SURVEY.md §8d): x ~ N(0,1) fp32;
     with `masked_tail`, clip 1 has its last ceil(T/4) frames marked as padding."""

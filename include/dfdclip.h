@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define DFD_ABI_VERSION 15
+#define DFD_ABI_VERSION 16
 
 enum { DFD_F32 = 0, DFD_BF16 = 1, DFD_FP8 = 2 /* OCP e4m3 ("e4m3fn"), one byte per element */ };
 
@@ -338,6 +338,24 @@ int dfd_quickgelu(const float* u, const float* du, float* out, int64_t n, const 
 int dfd_head_bwd(const float* raw_logits, const float* dlogits, const float* proj, const float* feat,
                  const float* dfeat_ext, float* dz, float* dfeat, float* dproj, int B, int D, int out_dim,
                  void* stream);
+
+/* CompInvEncoder pair loss (models.py:996-1051, under the aliasing of its predict: both operands are the ADAPTED
+ * K/V).  k, v [L, B*T*P, D] in `dtype` (f32 / bf16), rows (clip, frame, patch); clips 2i and
+ * 2i+1 form pair i, w = B/2 pairs (an odd last clip is unused).  With r = t*P + p the clip-local row,
+ *   S[r, c] = sum_{i, l, k|v} |A[2i][r, c] - A[2i+1][r, c]| / (w*L*2),
+ *   M[p', c] = mean over r in [p'*T, p'*T + T) of S[r, c]      (the reference's view(P, T, D).mean(1), no transpose)
+ *   match = ||M||_F / P.
+ * workspace >= dfd_compinv_loss_workspace(P, D) bytes, 16-byte aligned; M [P, D] f32 lands at its start.  match /
+ * norm (= ||M||_F) / recon (written 0: the reference's recon_loss is identically zero) are device f32 scalars;
+ * recon may be NULL.  Fixed summation order, no float atomics: bit-identical from run to run. */
+size_t dfd_compinv_loss_workspace(int P, int D);
+int dfd_compinv_loss_fwd(const void* k, const void* v, int dtype, int B, int T, int P, int D, int L, void* workspace,
+                         float* match, float* norm, float* recon, void* stream);
+/* Backward: dA[2i] = sign(A[2i] - A[2i+1]) * M[r / T, c] * g / (T*||M||*P*w*L*2), dA[2i+1] = -dA[2i]; zero where
+ * ||M|| = 0 and for an odd last clip.  `grad` = device f32 scalar d(loss)/d(match); workspace / norm as left by the
+ * forward.  dk, dv: same dtype and layout as k, v.  No host synchronisation. */
+int dfd_compinv_loss_bwd(const void* k, const void* v, int dtype, int B, int T, int P, int D, int L, const void* workspace,
+                         const float* norm, const float* grad, void* dk, void* dv, void* stream);
 
 #ifdef __cplusplus
 }
