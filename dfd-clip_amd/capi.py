@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libdfdclip_hip.so")
 
 F32, BF16 = 0, 1
 EPI_BIAS, EPI_BIAS_QUICKGELU, EPI_BIAS_RESIDUAL, EPI_PATCH_EMBED, EPI_QKV_EXPORT, EPI_RESIDUAL_POS = range(6)
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 _DTYPE = {torch.float32: F32, torch.bfloat16: BF16}
 FP8 = 2           # ABI code of OCP e4m3; stored in uint8 / torch.float8_e4m3fn tensors
@@ -112,6 +112,15 @@ SIGNATURES = {
                              c_void_p]),
     "dfd_head_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                              c_int, c_float, POINTER(DropoutDesc), c_void_p]),
+    "dfd_adapter_bn_workspace": (c_size_t, [c_int64, c_int, c_int]),
+    "dfd_adapter_bn_stats": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
+                                     c_int, c_float, c_float, c_void_p]),
+    "dfd_adapter_bn_apply": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     POINTER(DropoutDesc), c_int64, c_int, c_int, c_int, c_void_p]),
+    "dfd_adapter_bn_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   POINTER(DropoutDesc), c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p]),
+    "dfd_gelu_erf": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, POINTER(DropoutDesc), c_void_p]),
+    "dfd_gelu_erf_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int64, POINTER(DropoutDesc), c_void_p]),
     "dfd_compinv_loss_workspace": (c_size_t, [c_int, c_int]),
     "dfd_compinv_loss_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p]),
@@ -484,6 +493,84 @@ def head_fwd(x, gamma, beta, proj, feat, raw, logits, eps=1e-5, drop=None):
     _check(load_library().dfd_head_fwd(_ptr(x), x.stride(0), _ptr(gamma), _ptr(beta), _ptr(proj), _ptr(feat), _ptr(raw),
                                        _ptr(logits), B, D, proj.shape[1], eps, _drop(drop), _stream()), "dfd_head_fwd")
     return logits
+
+
+# ---- adapter structs without a LayerNorm: 768-bn, 768-xxx-768, linear (csrc/adapter_structs.hip) -----------------
+
+BN_EVAL, BN_TRAIN, BN_TRAIN_UPDATE = 0, 1, 2
+
+
+def adapter_bn_workspace_bytes(frames, patches, width):
+    return load_library().dfd_adapter_bn_workspace(frames, patches, width)
+
+
+def _bn_shape(t, frames, patches, width):
+    assert t.is_contiguous() and t.numel() == frames * patches * width, (tuple(t.shape), frames, patches, width)
+
+
+def adapter_bn_stats(y, stats, workspace, frames, patches, T, mode, running_mean=None, running_var=None,
+                     num_batches_tracked=None, momentum=0.1, eps=1e-5):
+    """stats [2, T] f32 = (mean, invstd) per frame channel t = frame % T of y [frames*patches, width]; mode BN_EVAL reads
+    the running statistics, BN_TRAIN_UPDATE also advances them (and num_batches_tracked) on the device."""
+    _dev(y, stats, workspace, running_mean, running_var, num_batches_tracked)
+    width = y.shape[-1]
+    _bn_shape(y, frames, patches, width)
+    assert stats.dtype == torch.float32 and stats.is_contiguous() and stats.numel() == 2 * T
+    for b in (running_mean, running_var):
+        assert b is None or (b.dtype == torch.float32 and b.is_contiguous() and b.numel() == T)
+    assert num_batches_tracked is None or num_batches_tracked.dtype == torch.int64
+    assert workspace.numel() * workspace.element_size() >= adapter_bn_workspace_bytes(frames, patches, width)
+    _check(load_library().dfd_adapter_bn_stats(_ptr(y), _DTYPE[y.dtype], _ptr(stats), _ptr(running_mean), _ptr(running_var),
+                                               _ptr(num_batches_tracked), _ptr(workspace), frames, patches, width, T, int(mode),
+                                               momentum, eps, _stream()), "dfd_adapter_bn_stats")
+    return stats
+
+
+def adapter_bn_apply(y, out, frames, patches, T, stats=None, gamma=None, beta=None, residual=None, pos=None, drop=None):
+    """out = residual + drop(γ_t·(y - μ_t)·invstd_t + β_t) + pos[t]; stats None: out = residual + drop(y) + pos."""
+    _dev(y, out, stats, gamma, beta, residual, pos)
+    width = y.shape[-1]
+    _bn_shape(y, frames, patches, width)
+    _bn_shape(out, frames, patches, width)
+    assert residual is None or (residual.dtype == out.dtype and residual.is_contiguous() and residual.numel() == out.numel())
+    assert pos is None or (pos.dtype == torch.float32 and pos.is_contiguous() and pos.numel() == T * width)
+    _check(load_library().dfd_adapter_bn_apply(_ptr(y), _DTYPE[y.dtype], _ptr(residual), _ptr(out), _DTYPE[out.dtype], _ptr(stats),
+                                               _ptr(gamma), _ptr(beta), _ptr(pos), _drop(drop), frames, patches, width, T,
+                                               _stream()), "dfd_adapter_bn_apply")
+    return out
+
+
+def adapter_bn_bwd(y, dout, dy, stats, gamma, dgamma, dbeta, workspace, frames, patches, T, train, drop=None):
+    """dy (dtype of y) and dγ / dβ [T] of out = drop(BN(y)); dout in y's dtype or f32."""
+    _dev(y, dout, dy, stats, gamma, dgamma, dbeta, workspace)
+    width = y.shape[-1]
+    for t in (y, dout, dy):
+        _bn_shape(t, frames, patches, width)
+    assert dy.dtype == y.dtype and dout.dtype in (y.dtype, torch.float32)
+    assert workspace.numel() * workspace.element_size() >= adapter_bn_workspace_bytes(frames, patches, width)
+    _check(load_library().dfd_adapter_bn_bwd(_ptr(y), _ptr(dout), _DTYPE[dout.dtype], _ptr(dy), _DTYPE[y.dtype], _ptr(stats),
+                                             _ptr(gamma), _ptr(dgamma), _ptr(dbeta), _drop(drop), _ptr(workspace), frames,
+                                             patches, width, T, int(bool(train)), _stream()), "dfd_adapter_bn_bwd")
+    return dy
+
+
+def gelu_erf(a, out, drop=None):
+    """out = drop(GELU(a)), nn.GELU()'s erf form."""
+    _dev(a, out)
+    assert a.is_contiguous() and out.is_contiguous() and a.numel() == out.numel()
+    _check(load_library().dfd_gelu_erf(_ptr(a), _DTYPE[a.dtype], _ptr(out), _DTYPE[out.dtype], a.numel(), _drop(drop), _stream()),
+           "dfd_gelu_erf")
+    return out
+
+
+def gelu_erf_bwd(a, dh, da, drop=None):
+    """da = GELU'(a)·drop(dh)."""
+    _dev(a, dh, da)
+    assert a.is_contiguous() and dh.is_contiguous() and da.is_contiguous() and a.numel() == dh.numel() == da.numel()
+    assert dh.dtype == da.dtype
+    _check(load_library().dfd_gelu_erf_bwd(_ptr(a), _DTYPE[a.dtype], _ptr(dh), _DTYPE[dh.dtype], _ptr(da), _DTYPE[da.dtype], a.numel(),
+                                           _drop(drop), _stream()), "dfd_gelu_erf_bwd")
+    return da
 
 
 def dropout(x, out, drop):

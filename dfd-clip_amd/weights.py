@@ -94,8 +94,9 @@ def decoder_schema(arch, num_frames, n_blocks, out_dims, temporal_position=True,
     return s
 
 
-def adapter_schema(arch, n_blocks, struct_type, x):
-    """`CompInvAdapter` parameters (reference `src/models.py:783-928`), the LayerNorm variants."""
+def adapter_schema(arch, n_blocks, struct_type, x, num_frames=None):
+    """`CompInvAdapter` state (reference `src/models.py:783-928`): parameters, and for "768-bn" its BatchNorm2d(num_frames)
+    buffers (`running_mean` / `running_var` [T], `num_batches_tracked` [] int64)."""
     res, patch, width, layers, heads, _ = ARCHS[arch]
     patches = (res // patch) ** 2
     s = OrderedDict()
@@ -117,6 +118,19 @@ def adapter_schema(arch, n_blocks, struct_type, x):
                 s[p + "2.weight"] = (x,)
                 s[p + "2.bias"] = (x,)
                 s[p + ("4.weight" if struct_type == "768-x-768" else "3.weight")] = (width, x)
+            elif struct_type == "768-bn":  # Linear(768, 768), BatchNorm2d(num_frames), Dropout
+                if num_frames is None:
+                    raise ValueError("768-bn: the BatchNorm's channel count is num_frames")
+                s[p + "0.weight"] = (768, 768)
+                for k in ("1.weight", "1.bias", "1.running_mean", "1.running_var"):
+                    s[p + k] = (num_frames,)
+                s[p + "1.num_batches_tracked"] = ()
+            elif struct_type == "768-xxx-768":  # Linear, GELU, Dropout, Linear, GELU, Dropout, Linear, Dropout
+                s[p + "0.weight"] = (x, width)
+                s[p + "3.weight"] = (x, x)
+                s[p + "6.weight"] = (width, x)
+            elif struct_type == "linear":
+                s[p + "0.weight"] = (width, width)
             else:
                 raise NotImplementedError(struct_type)
     return s
@@ -127,6 +141,12 @@ def _fill(rng, name, shape):
     O(1); LayerNorm gains near 1 and all biases small but non-zero so that every gain/bias
     path is exercised by the parity tests."""
     leaf = name.split(".")[-1]
+    if leaf == "num_batches_tracked":  # BatchNorm buffers: a few steps already taken, statistics well off (0, 1)
+        return torch.tensor(int(rng.integers(1, 100)), dtype=torch.int64)
+    if leaf == "running_mean":
+        return torch.from_numpy(np.ascontiguousarray(0.1 * rng.standard_normal(shape), dtype=np.float32))
+    if leaf == "running_var":
+        return torch.from_numpy(np.ascontiguousarray(np.exp(0.3 * rng.standard_normal(shape)) * 0.8, dtype=np.float32))
     is_ln = ".ln_" in name or name.startswith("ln_") or (name.split(".")[-2:-1] == ["1"]) or \
         (name.split(".")[-2:-1] == ["2"] and len(shape) == 1)
     if is_ln and leaf == "weight":
@@ -185,12 +205,12 @@ def random_state_dict(config, num_frames, seed=0):
         sd["ranking_transform_param"] = _fill(rng, "proj", (width, 1))
     if config.adapter.type != "none":
         st = config.adapter.struct
-        for k, shp in adapter_schema(arch, len(lidx), st.type, int(st.x)).items():
+        for k, shp in adapter_schema(arch, len(lidx), st.type, int(st.x) if "x" in st else 0, num_frames).items():
             sd["adapter." + k] = _fill(rng, k, shp)
     return sd
 
 
-def random_compinv_state_dict(config, seed=0):
+def random_compinv_state_dict(config, seed=0, num_frames=None):
     """Seeded fp32 `CompInvEncoder` state_dict (reference key names): `encoder.*` as in `random_state_dict`, then
     `adapter.l{i}_{k|v}.*` for the tapped layers."""
     arch = config.architecture
@@ -200,7 +220,8 @@ def random_compinv_state_dict(config, seed=0):
     for k, shp in encoder_schema(arch).items():
         sd["encoder." + k] = _fill(rng, k, shp)
     st = config.adapter.struct
-    for k, shp in adapter_schema(arch, len(resolve_layer_indices(config, layers)), st.type, int(st.x)).items():
+    for k, shp in adapter_schema(arch, len(resolve_layer_indices(config, layers)), st.type, int(st.x) if "x" in st else 0,
+                                 num_frames).items():
         sd["adapter." + k] = _fill(rng, k, shp)
     return sd
 

@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define DFD_ABI_VERSION 16
+#define DFD_ABI_VERSION 17
 
 enum { DFD_F32 = 0, DFD_BF16 = 1, DFD_FP8 = 2 /* OCP e4m3 ("e4m3fn"), one byte per element */ };
 
@@ -356,6 +356,39 @@ int dfd_compinv_loss_fwd(const void* k, const void* v, int dtype, int B, int T, 
  * forward.  dk, dv: same dtype and layout as k, v.  No host synchronisation. */
 int dfd_compinv_loss_bwd(const void* k, const void* v, int dtype, int B, int T, int P, int D, int L, const void* workspace,
                          const float* norm, const float* grad, void* dk, void* dv, void* stream);
+
+/* ---- CompInvAdapter structs without a LayerNorm (models.py:877-922): dfd-clip_amd/csrc/adapter_structs.hip ----
+ * "768-bn":  y = kv·W0ᵀ (dfd_gemm), then BatchNorm2d(T) over the packed [frames, patches, width] y: channel t = frame % T,
+ * statistics over (clip, patch, width), n = frames/T·patches·width values per channel.  stats [2, T] f32 = (mean, invstd).
+ * Deterministic: per-(frame, 8192-element chunk) partials in `workspace`, merged per channel in a fixed order (Chan's
+ * update); bit-identical from run to run.  workspace >= dfd_adapter_bn_workspace(...) bytes, 16-byte aligned.
+ * mode 0 (eval): stats from running_mean / running_var, y unread; 1: batch mean and biased variance; 2: as 1, then
+ * running ← (1-momentum)·running + momentum·batch (variance unbiased by n/(n-1)) and ++num_batches_tracked, on the
+ * device (a captured graph advances them once per replay).  running_* f32 [T], num_batches_tracked int64 [1]. */
+size_t dfd_adapter_bn_workspace(int64_t frames, int patches, int width);
+int dfd_adapter_bn_stats(const void* y, int dtype, float* stats, float* running_mean, float* running_var,
+                         int64_t* num_batches_tracked, void* workspace, int64_t frames, int patches, int width, int T, int mode,
+                         float momentum, float eps, void* stream);
+/* out = residual + drop(γ_t·(y - μ_t)·invstd_t + β_t) + pos[t]  on [frames, patches, width], t = frame % T, one rounding
+ * to `dtype`.  stats NULL: out = residual + drop(y) + pos (the "linear" struct's epilogue: y = kv·W0ᵀ in f32, residual
+ * NULL).  residual NULL = none; residual may alias out (in place); pos [T, width] f32 or NULL; drop NULL = none (element
+ * index = flat position).  width % 8 == 0, 16-byte aligned buffers. */
+int dfd_adapter_bn_apply(const void* y, int y_dtype, const void* residual, void* out, int dtype, const float* stats,
+                         const float* gamma, const float* beta, const float* pos, const dfd_dropout_t* drop, int64_t frames,
+                         int patches, int width, int T, void* stream);
+/* Backward of dfd_adapter_bn_apply (with stats) w.r.t. y and the affine: dz = drop(dout) (same descriptor as the
+ * forward), dbeta[t] = Σdz, dgamma[t] = Σdz·ŷ (ŷ = (y - μ)·invstd from `stats` as the forward used them; fixed order),
+ * then dy = γ·invstd·(dz - dbeta/n - ŷ·dgamma/n) (train) or γ·invstd·dz (train == 0: running statistics).  y / dy in
+ * `dtype`, dout in dtype or f32.  Running statistics are not touched.  workspace as for dfd_adapter_bn_stats. */
+int dfd_adapter_bn_bwd(const void* y, const void* dout, int dout_dtype, void* dy, int dtype, const float* stats,
+                       const float* gamma, float* dgamma, float* dbeta, const dfd_dropout_t* drop, void* workspace,
+                       int64_t frames, int patches, int width, int T, int train, void* stream);
+/* "768-xxx-768": out = drop(GELU(a)) with nn.GELU()'s exact form 0.5·a·(1 + erf(a/√2)); backward
+ * da = GELU'(a)·drop(dh) from the saved pre-activation a.  n % 8 == 0, 16-byte aligned; f32 / bf16 in any mix (dh and
+ * da share a dtype).  In place allowed where the dtypes agree. */
+int dfd_gelu_erf(const void* a, int a_dtype, void* out, int out_dtype, int64_t n, const dfd_dropout_t* drop, void* stream);
+int dfd_gelu_erf_bwd(const void* a, int a_dtype, const void* dh, int dh_dtype, void* da, int da_dtype, int64_t n,
+                     const dfd_dropout_t* drop, void* stream);
 
 #ifdef __cplusplus
 }
