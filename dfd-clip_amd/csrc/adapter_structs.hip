@@ -9,6 +9,7 @@
 // no float atomics, no E[y²] - E[y]², which cancels at the 2.4 M values of a channel at B16xT30).  The backward's two
 // sums (Σdz, Σdz·ŷ) take the same partial-slab route.  All streaming kernels move 16 bytes per lane per access.
 #include "dropout.hpp"
+#include "gelu.hpp"
 
 namespace {
 
@@ -42,10 +43,7 @@ template <> struct V8<bf16_t> {
   }
 };
 
-__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
-__device__ __forceinline__ float gelu_erf_grad(float z) {
-  return 0.5f * (1.0f + erff(z * 0.70710678118654752f)) + z * 0.3989422804014327f * __expf(-0.5f * z * z);
-}
+// gelu_erf / gelu_erf_grad: gelu.hpp (shared with the GEMM epilogue)
 
 // (n, mean, M2) of a set, merged with another (Chan et al.); n = 0 on either side is the identity
 struct Moments {

@@ -12,6 +12,7 @@
 // Both A and W are K-contiguous, so both MFMA operands are plain 16-byte row reads: lane
 // (r = lane&31, h = lane>>5) holds A[row r][k-slice h] and W[row r][k-slice h].
 #include "gemm_args.hpp"
+#include "gelu.hpp"
 
 namespace {
 
@@ -32,6 +33,8 @@ __device__ __forceinline__ void epilogue_elem(const GemmArgs& a, int64_t m, int 
     store_c<CT>(a.C, m * a.ldc + n, acc + (a.bias ? a.bias[n] : 0.f));
   } else if constexpr (EPI == DFD_EPI_BIAS_QUICKGELU) {
     store_c<CT>(a.C, m * a.ldc + n, quick_gelu(acc + (a.bias ? a.bias[n] : 0.f)));
+  } else if constexpr (EPI == DFD_EPI_BIAS_GELU) {
+    store_c<CT>(a.C, m * a.ldc + n, gelu_erf(acc + (a.bias ? a.bias[n] : 0.f)));
   } else if constexpr (EPI == DFD_EPI_BIAS_RESIDUAL) {
     float* c = static_cast<float*>(a.C) + m * a.ldc + n;
     *c = *c + (acc + (a.bias ? a.bias[n] : 0.f));
@@ -196,6 +199,7 @@ int launch_gemm128(const GemmArgs& a, int epi, hipStream_t st) {
   switch (epi) {
     EPI_CASE(DFD_EPI_BIAS)
     EPI_CASE(DFD_EPI_BIAS_QUICKGELU)
+    EPI_CASE(DFD_EPI_BIAS_GELU)
     EPI_CASE(DFD_EPI_QKV_EXPORT)
     EPI_CASE(DFD_EPI_RESIDUAL_POS)
     default:

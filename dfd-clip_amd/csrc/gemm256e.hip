@@ -1,5 +1,5 @@
 // Persistent 256x256 GEMM with a PING-PONG K loop: the encoder's GEMM since round 3 (bf16 and e4m3 operands; epilogues
-// BIAS, BIAS_QUICKGELU, QKV_EXPORT with a bf16 C, e4m3 C for the first two of the fp8 form; reference clip/model.py:186,
+// BIAS, BIAS_QUICKGELU, BIAS_GELU (bf16 operands only), QKV_EXPORT with a bf16 C, e4m3 C for the first two of the fp8 form; reference clip/model.py:186,
 // :197, :208-212).  gemm256p.hip (round 2) stays as the fallback for the K depths this loop does not serve.
 //
 // gemm256p runs the same software-pipelined instruction stream in all eight waves: the two waves of a SIMD reach their
@@ -43,6 +43,7 @@
 #include <unordered_map>
 
 #include "gemm256p_common.hpp"
+#include "gelu.hpp"
 
 namespace {
 
@@ -494,6 +495,9 @@ __global__ __launch_bounds__(512) void gemm256e_kernel(const GemmArgs a, int til
 #pragma unroll
           for (int e = 0; e < 4; ++e) d[e] = __builtin_amdgcn_rcpf(d[e]);
           v = v * d;
+        } else if constexpr (EPI == DFD_EPI_BIAS_GELU) {
+          // exact-erf GELU (gelu.hpp): the same scalar function as the general kernel, so the two agree bit for bit
+          v = gelu_erf4(v);
         }
         return v;
       };
@@ -789,6 +793,8 @@ int dfd_gemm256e_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st) {
       return launch256e<DFD_EPI_BIAS, false, false>(a, st);
     case DFD_EPI_BIAS_QUICKGELU:
       return launch256e<DFD_EPI_BIAS_QUICKGELU, false, false>(a, st);
+    case DFD_EPI_BIAS_GELU:
+      return launch256e<DFD_EPI_BIAS_GELU, false, false>(a, st);
     case DFD_EPI_QKV_EXPORT: {
       if (check_export_e(a)) return 1;
       GemmArgs b = a;

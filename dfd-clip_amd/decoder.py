@@ -112,6 +112,12 @@ class Decoder(RuntimeStateMixin, nn.Module):
         # decoder blocks start from the encoder layer they read (models.py:226-229)
         for b, l in enumerate(self.layer_indices):
             src, dst = enc.transformer.resblocks[l], self.transformer.resblocks[b]
+            if hasattr(src, "norm1"):  # a DINOv2 block: norm1 / norm2, mlp.fc1 / fc2 (models.py:192-209)
+                dst.ln_1.load_state_dict(src.norm1.state_dict())
+                dst.ln_2.load_state_dict(src.norm2.state_dict())
+                names = {"fc1": "c_fc", "fc2": "c_proj"}
+                dst.mlp.load_state_dict({names[k.split(".")[0]] + "." + k.split(".", 1)[1]: v for k, v in src.mlp.state_dict().items()})
+                continue
             dst.ln_1.load_state_dict(src.ln_1.state_dict())
             dst.ln_2.load_state_dict(src.ln_2.state_dict())
             dst.mlp.load_state_dict(src.mlp.state_dict())

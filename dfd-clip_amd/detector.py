@@ -11,6 +11,8 @@ libdfdclip_hip.so; PyTorch supplies device memory, streams and the tiny per-samp
 `precision` is the only addition to the reference signature: "fp32" is the parity path
 (logits within 1e-3 of the reference's fp32 CPU result), "bf16" the throughput path, "fp8" the bf16 path
 with the encoder's large projections on e4m3 matrix-core operands (BASELINE configs[4]; `calibrate_fp8`).
+`config.foundation` selects the frozen tower: "clip" (`architecture` names it) or "dinov2" (ViT-B/14, dinov2.py;
+fp32 and bf16; a CLIP model name in `architecture` is ignored as in the reference, see `weights.model_arch`).
 """
 import contextlib
 import logging
@@ -29,7 +31,7 @@ from .config import default_detector_config
 from .adapter import CompInvAdapter
 from .decoder import Decoder
 from .encoder import RuntimeStateMixin, VisionTransformer
-from .weights import ARCHS, resolve_layer_indices
+from .weights import ARCHS, model_arch, resolve_layer_indices
 
 _ENC_STREAMS = {}  # device -> the process's high-priority encoder stream (`Detector._encode`)
 
@@ -169,9 +171,12 @@ class ClipTransform:
     MEAN = (0.48145466, 0.4578275, 0.40821073)
     STD = (0.26862954, 0.26130258, 0.27577711)
 
-    def __init__(self, n_px, antialias=True):
+    def __init__(self, n_px, antialias=True, mean=None, std=None):
         self.n_px = n_px
         self.antialias = antialias
+        # per foundation (reference src/models.py:756-779): CLIP's statistics unless given (DINOv2: ImageNet's)
+        self.mean = tuple(mean) if mean is not None else self.MEAN
+        self.std = tuple(std) if std is not None else self.STD
 
     def geometry(self, h, w):
         s, l = (h, w) if h <= w else (w, h)
@@ -185,7 +190,7 @@ class ClipTransform:
             lead = x.shape[:-3]
             out = torch.empty(x.numel() // (3 * x.shape[-2] * x.shape[-1]), 3, self.n_px, self.n_px, device=x.device)
             tile = max(d for d in range(1, 33) if self.n_px % d == 0)  # work tile of the kernel, any divisor
-            capi.preprocess_u8(x.reshape(-1, *x.shape[-3:]).contiguous(), out, self.n_px, tile, self.MEAN, self.STD,
+            capi.preprocess_u8(x.reshape(-1, *x.shape[-3:]).contiguous(), out, self.n_px, tile, self.mean, self.std,
                                antialias=self.antialias, patch_rows=False)
             return out.view(*lead, 3, self.n_px, self.n_px)
         was_u8 = x.dtype == torch.uint8
@@ -198,8 +203,8 @@ class ClipTransform:
                 x = x.round().clamp(0, 255)
         x = x[..., top:top + self.n_px, left:left + self.n_px]
         x = x.float() / 255.0 if was_u8 else x
-        mean = torch.tensor(self.MEAN, device=x.device).view(1, 3, 1, 1)
-        std = torch.tensor(self.STD, device=x.device).view(1, 3, 1, 1)
+        mean = torch.tensor(self.mean, device=x.device).view(1, 3, 1, 1)
+        std = torch.tensor(self.std, device=x.device).view(1, 3, 1, 1)
         return (x - mean) / std
 
 
@@ -249,11 +254,17 @@ class Detector(RuntimeStateMixin, nn.Module):
         self.config = config
         self.precision = precision
         self.num_frames = num_frames
-        if config.foundation != "clip":
-            raise NotImplementedError("only the CLIP foundation is built (DINOv2 is out of scope)")
+        if config.foundation not in ("clip", "dinov2"):
+            raise NotImplementedError(f"foundation = {config.foundation!r} (built: 'clip', 'dinov2')")
         ctx = accelerator.main_process_first() if accelerator is not None else contextlib.nullcontext()
         with ctx:
-            self.encoder = disable_gradients(load_clip_visual(config.architecture, precision))
+            if config.foundation == "dinov2":
+                # ViT-B/14 whichever CLIP model `architecture` names, as in the reference (src/models.py:441-444);
+                # `weights.model_arch` also lets it name a DINOv2 geometry and refuses anything else
+                from .dinov2 import DINOv2
+                self.encoder = disable_gradients(DINOv2(model_arch(config), precision=precision))
+            else:
+                self.encoder = disable_gradients(load_clip_visual(config.architecture, precision))
         self.decode_mode = config.decode_mode
         self.out_dim = config.out_dim
         self.weight_decay = config.weight_decay
@@ -264,7 +275,7 @@ class Detector(RuntimeStateMixin, nn.Module):
         self.layer_indices = resolve_layer_indices(config, len(self.encoder.transformer.resblocks))
         self.decoder = Decoder(self, config, num_frames)
         self.adapter = self._build_adapter(config, num_frames)
-        self.transform = ClipTransform(self.encoder.input_resolution)
+        self.transform = ClipTransform(self.encoder.input_resolution, mean=self.encoder.pixel_mean, std=self.encoder.pixel_std)
         # opt-in: replay the decoder's training-step kernels as HIP graphs (fixed batch shape; see decoder.py)
         self.static_graphs = False
         self._kv_static = None

@@ -98,20 +98,21 @@ class Transformer(_Holder):
         self.resblocks = nn.Sequential(*[ResidualAttentionBlock(width, heads) for _ in range(layers)])
 
 
+def _invalidate_after_load(module, incompatible_keys):
+    module.invalidate()
+
+
 class VisionTransformer(RuntimeStateMixin, nn.Module):
     _RUNTIME_STATE = {"_prepared": None, "_ws": {}, "_side_streams": [], "_calib": None}
+    # What another tower of the same token geometry changes (dinov2.py): the LayerNorm epsilon, the activation
+    # epilogue of the MLP's first GEMM, whether a ln_pre follows the patch embedding (`_stage` leaves its entry None),
+    # the parameters (`__init__`, `_param_device`) and how they are staged for the kernels (`_stage`).
+    ln_eps = 1e-5
+    act_epilogue = capi.EPI_BIAS_QUICKGELU
 
     def __init__(self, input_resolution, patch_size, width, layers, heads, output_dim, precision="bf16"):
         super().__init__()
-        assert width % heads == 0 and width // heads == 64, "kernels are built for 64-wide heads"
-        assert precision in ("fp32", "bf16", "fp8")
-        self.input_resolution = input_resolution
         self.output_dim = output_dim
-        self.width = width
-        self.layers = layers
-        self.heads = heads
-        self.patch_size = patch_size
-        self.precision = precision
         self.conv1 = nn.Conv2d(3, width, kernel_size=patch_size, stride=patch_size, bias=False)
         scale = width ** -0.5
         self.class_embedding = nn.Parameter(scale * torch.randn(width))
@@ -120,6 +121,21 @@ class VisionTransformer(RuntimeStateMixin, nn.Module):
         self.transformer = Transformer(width, layers, heads)
         self.ln_post = nn.LayerNorm(width)
         self.proj = nn.Parameter(scale * torch.randn(width, output_dim))
+        self._init_runtime(input_resolution, patch_size, width, layers, heads, precision)
+
+    def _init_runtime(self, input_resolution, patch_size, width, layers, heads, precision):
+        """Geometry, precision and every knob that is not a parameter (shared by the towers)."""
+        assert width % heads == 0 and width // heads == 64, "kernels are built for 64-wide heads"
+        assert precision in ("fp32", "bf16", "fp8")
+        self.input_resolution = input_resolution
+        self.width = width
+        self.layers = layers
+        self.heads = heads
+        self.patch_size = patch_size
+        self.precision = precision
+        # a load through a parent module (`Detector.load_state_dict`) never calls this module's own `load_state_dict`:
+        # the staged operands are dropped by a post-load hook, which fires either way
+        self.register_load_state_dict_post_hook(_invalidate_after_load)
         self._prepared = None
         self._ws = {}
         self.frame_chunk = 0  # frames per pass; 0 = the batch split evenly over `streams`
@@ -243,12 +259,20 @@ class VisionTransformer(RuntimeStateMixin, nn.Module):
         self._fp8 = None
         return out
 
+    def _param_device(self):
+        return self.class_embedding.device
+
     def _prepare(self):
         if self._prepared is not None:
             return self._prepared
-        dev = self.class_embedding.device
+        dev = self._param_device()
         if dev.type != "cuda":
             raise capi.DfdError("the encoder runs on HIP kernels only: move the model to a GPU (.to('cuda'))")
+        self._prepared = self._stage(dev)
+        return self._prepared
+
+    def _stage(self, dev):
+        """Device-side operands of the kernels, derived from the parameters (rebuilt after they change)."""
         act = self.act_dtype
         kreal = 3 * self.patch_size ** 2
         kpad = (kreal + 63) // 64 * 64  # multiple of the tuned GEMM's K step (ViT-L/14: 588 -> 640); pad columns are zero
@@ -276,7 +300,6 @@ class VisionTransformer(RuntimeStateMixin, nn.Module):
                 w_out=blk.attn.out_proj.weight.detach().to(act).contiguous(), b_out=f32(blk.attn.out_proj.bias),
                 w_fc=blk.mlp.c_fc.weight.detach().to(act).contiguous(), b_fc=f32(blk.mlp.c_fc.bias),
                 w_proj=blk.mlp.c_proj.weight.detach().to(act).contiguous(), b_proj=f32(blk.mlp.c_proj.bias)))
-        self._prepared = p
         return p
 
     def _workspace(self, n, keep_layers, slot=0):
@@ -285,7 +308,7 @@ class VisionTransformer(RuntimeStateMixin, nn.Module):
         key = (n, self.precision, keep_layers, slot)
         ws = self._ws.get(key)
         if ws is None:
-            dev = self.class_embedding.device
+            dev = self._param_device()
             act, D = self.act_dtype, self.width
             M = n * self.tokens
             Mp = (M + 255) // 256 * 256
@@ -339,7 +362,7 @@ class VisionTransformer(RuntimeStateMixin, nn.Module):
                   tokens=self.tokens)
         ws["pending"] = 0
         # ln_pre is not run here: the first block's ln_1 does it in the same pass over the rows (`_ln`, dfd_layernorm2)
-        ws["ln_pre"] = p["ln_pre"]
+        ws["ln_pre"] = p["ln_pre"]  # None: a tower without one
 
     def _ln(self, ws, gb, M, store=True, q=None, discard_x=False):
         """h = LayerNorm(x).  On the bf16 path the residual branches that have not been added yet
@@ -353,24 +376,24 @@ class VisionTransformer(RuntimeStateMixin, nn.Module):
         if pre is not None:  # first LayerNorm after the patch embedding: x <- ln_pre(x), h = ln_1(x), one pass
             assert pend == 0
             if self.width <= 2048:
-                capi.layernorm2(x[:M], pre[0], pre[1], gb[0], gb[1], h[:M], out_inv_scale=inv)
+                capi.layernorm2(x[:M], pre[0], pre[1], gb[0], gb[1], h[:M], eps=self.ln_eps, out_inv_scale=inv)
             else:
-                capi.layernorm(x[:M], pre[0], pre[1], x[:M])
-                capi.layernorm(x[:M], gb[0], gb[1], h[:M], out_inv_scale=inv)
+                capi.layernorm(x[:M], pre[0], pre[1], x[:M], eps=self.ln_eps)
+                capi.layernorm(x[:M], gb[0], gb[1], h[:M], eps=self.ln_eps, out_inv_scale=inv)
         elif pend == 0:
-            capi.layernorm(x[:M], gb[0], gb[1], h[:M], out_inv_scale=inv)
+            capi.layernorm(x[:M], gb[0], gb[1], h[:M], eps=self.ln_eps, out_inv_scale=inv)
         elif discard_x:
             # last block of an extraction pass (K and V thirds only): nothing reads the residual stream after this
             # LayerNorm, so the sum is normalised without being stored (290 MB of writes less at B16xT30)
             capi.add_layernorm(x[:M], ws["delta"][:M], gb[0], gb[1], h[:M], delta2=ws["delta2"][:M] if pend == 2 else None,
-                               store_x=False, out_inv_scale=inv)
+                               store_x=False, eps=self.ln_eps, out_inv_scale=inv)
             ws["pending"] = 0
         elif not store:
             assert pend == 1
-            capi.add_layernorm(x[:M], ws["delta"][:M], gb[0], gb[1], h[:M], store_x=False, out_inv_scale=inv)
+            capi.add_layernorm(x[:M], ws["delta"][:M], gb[0], gb[1], h[:M], store_x=False, eps=self.ln_eps, out_inv_scale=inv)
         else:
             capi.add_layernorm(x[:M], ws["delta"][:M], gb[0], gb[1], h[:M], delta2=ws["delta2"][:M] if pend == 2 else None,
-                               out_inv_scale=inv)
+                               eps=self.ln_eps, out_inv_scale=inv)
             ws["pending"] = 0
 
     def _residual(self, ws, a, w, b, M, spare_cus=0, spare_if_free=False):
@@ -442,7 +465,7 @@ class VisionTransformer(RuntimeStateMixin, nn.Module):
             self._ln(ws, bp["ln2"], M, store=False)
             if calib is not None:
                 calib.append(ws["h"][:M].abs().max())
-            capi.gemm(ws["h"], bp["w_fc"], ws["u"], bp["b_fc"], capi.EPI_BIAS_QUICKGELU, m=M, stream_out=so["fc"], spare_cus=sp_fc, spare_if_free=free)
+            capi.gemm(ws["h"], bp["w_fc"], ws["u"], bp["b_fc"], self.act_epilogue, m=M, stream_out=so["fc"], spare_cus=sp_fc, spare_if_free=free)
             if calib is not None:
                 calib.append(ws["u"][:M].abs().max())
             self._residual(ws, ws["u"], bp["w_proj"], bp["b_proj"], M, spare_cus=sp_proj, spare_if_free=free)

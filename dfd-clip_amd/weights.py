@@ -25,7 +25,65 @@ ARCHS = {
     "tiny": (32, 16, 128, 2, 2, 64),
     "small": (224, 16, 256, 3, 4, 64),
     "small14": (224, 14, 128, 2, 2, 64),  # ViT-L/14's token geometry: 14x14 patches (K = 588), 257 tokens
+    # DINOv2 towers (`config.foundation == "dinov2"`; dinov2.py): resolution of the RUN, no output projection.  The
+    # reference wrapper hard-codes ViT-B/14 (src/models.py:368); `dino_tiny` is the test geometry
+    "dinov2_vitb14": (224, 14, 768, 12, 12, 0),
+    "dino_tiny": (28, 14, 128, 2, 2, 0),
 }
+# ... and the image size their `pos_embed` is stored for (518 px = a 37x37 grid, resampled to the run's grid; the tiny
+# one 70 px = 5x5 -> 2x2)
+DINO_IMG_SIZE = {"dinov2_vitb14": 518, "dino_tiny": 70}
+
+
+# the model names the reference's `clip.load` knows (src/clip/clip.py:30-40): what a reference config carries in `architecture`
+REFERENCE_CLIP_NAMES = ("RN50", "RN101", "RN50x4", "RN50x16", "RN50x64", "ViT-B/32", "ViT-B/16", "ViT-L/14", "ViT-L/14@336px")
+
+
+def model_arch(config):
+    """The `ARCHS` row a config runs on.  With `foundation: dinov2` the reference ignores `architecture` and builds
+    ViT-B/14 (src/models.py:441-444), and its shipped dino configs still carry `architecture: ViT-B/16`.  So here: one
+    of the reference's CLIP model names (or no entry) is ignored in the same way; the name of a DINOv2 geometry of
+    `DINO_IMG_SIZE` selects it (`dino_tiny` for tests); anything else -- this project's CLIP test geometries such as
+    "tiny" -- is refused, rather than answered with an 86 M-parameter ViT-B/14 nobody named."""
+    if "foundation" in config and config.foundation == "dinov2":
+        name = config.architecture if "architecture" in config else None
+        if name in DINO_IMG_SIZE:
+            return name
+        if name is None or name in REFERENCE_CLIP_NAMES:
+            return "dinov2_vitb14"
+        raise NotImplementedError(f"foundation 'dinov2' with architecture {name!r}: no DINOv2 tower of that geometry is built "
+                                  f"(built: {sorted(DINO_IMG_SIZE)}; the reference's CLIP model names are ignored, as in the reference)")
+    return config.architecture
+
+
+def dinov2_schema(arch):
+    """`DINOv2.state_dict()` (reference src/models.py:364-391 around dinov2/models/vision_transformer.py): key -> shape."""
+    res, patch, width, layers, heads, _ = ARCHS[arch]
+    s = OrderedDict()
+    s["backbone.cls_token"] = (1, 1, width)
+    s["backbone.pos_embed"] = (1, (DINO_IMG_SIZE[arch] // patch) ** 2 + 1, width)
+    s["backbone.mask_token"] = (1, width)
+    s["backbone.patch_embed.proj.weight"] = (width, 3, patch, patch)
+    s["backbone.patch_embed.proj.bias"] = (width,)
+    for l in range(layers):
+        p = f"backbone.blocks.{l}."
+        s[p + "norm1.weight"] = (width,)
+        s[p + "norm1.bias"] = (width,)
+        s[p + "attn.qkv.weight"] = (3 * width, width)
+        s[p + "attn.qkv.bias"] = (3 * width,)
+        s[p + "attn.proj.weight"] = (width, width)
+        s[p + "attn.proj.bias"] = (width,)
+        s[p + "ls1.gamma"] = (width,)
+        s[p + "norm2.weight"] = (width,)
+        s[p + "norm2.bias"] = (width,)
+        s[p + "mlp.fc1.weight"] = (4 * width, width)
+        s[p + "mlp.fc1.bias"] = (4 * width,)
+        s[p + "mlp.fc2.weight"] = (width, 4 * width)
+        s[p + "mlp.fc2.bias"] = (width,)
+        s[p + "ls2.gamma"] = (width,)
+    s["backbone.norm.weight"] = (width,)
+    s["backbone.norm.bias"] = (width,)
+    return s
 
 
 def encoder_schema(arch):
@@ -147,7 +205,11 @@ def _fill(rng, name, shape):
         return torch.from_numpy(np.ascontiguousarray(0.1 * rng.standard_normal(shape), dtype=np.float32))
     if leaf == "running_var":
         return torch.from_numpy(np.ascontiguousarray(np.exp(0.3 * rng.standard_normal(shape)) * 0.8, dtype=np.float32))
-    is_ln = ".ln_" in name or name.startswith("ln_") or (name.split(".")[-2:-1] == ["1"]) or \
+    if leaf == "gamma":  # LayerScale: well off 1 and of both signs of deviation, so a folding error shows
+        return torch.from_numpy(np.ascontiguousarray(np.exp(0.4 * rng.standard_normal(shape)) * 0.7, dtype=np.float32))
+    if leaf in ("cls_token", "pos_embed", "mask_token"):
+        return torch.from_numpy(np.ascontiguousarray((shape[-1] ** -0.5) * rng.standard_normal(shape), dtype=np.float32))
+    is_ln = ".norm" in name or ".ln_" in name or name.startswith("ln_") or (name.split(".")[-2:-1] == ["1"]) or \
         (name.split(".")[-2:-1] == ["2"] and len(shape) == 1)
     if is_ln and leaf == "weight":
         a = 1.0 + 0.05 * rng.standard_normal(shape)
@@ -179,11 +241,12 @@ def random_state_dict(config, num_frames, seed=0):
     """Seeded fp32 `Detector` state_dict (reference key names).  The decoder's ln_1 / ln_2 /
     mlp start as copies of encoder layer `layer_indices[i]`, as the reference's
     `_apply_reference` does (`src/models.py:226-229`, concat_ref == 0)."""
-    arch = config.architecture
+    arch = model_arch(config)
+    dino = "foundation" in config and config.foundation == "dinov2"
     res, patch, width, layers, heads, _ = ARCHS[arch]
     rng = np.random.default_rng(seed)
     sd = OrderedDict()
-    for k, shp in encoder_schema(arch).items():
+    for k, shp in (dinov2_schema(arch) if dino else encoder_schema(arch)).items():
         sd["encoder." + k] = _fill(rng, k, shp)
     lidx = resolve_layer_indices(config, layers)
     op = config.op_mode
@@ -199,8 +262,13 @@ def random_state_dict(config, num_frames, seed=0):
         for b, l in enumerate(lidx):
             for part in ("ln_1.weight", "ln_1.bias", "ln_2.weight", "ln_2.bias", "mlp.c_fc.weight",
                          "mlp.c_fc.bias", "mlp.c_proj.weight", "mlp.c_proj.bias"):
-                sd[f"decoder.transformer.resblocks.{b}.{part}"] = \
-                    sd[f"encoder.transformer.resblocks.{l}.{part}"].clone()
+                src = f"encoder.transformer.resblocks.{l}.{part}"
+                if dino:  # norm1 / norm2 / mlp.fc1 / mlp.fc2 of the backbone's block (reference src/models.py:192-209)
+                    theirs = part
+                    for a_, b_ in (("ln_1", "norm1"), ("ln_2", "norm2"), ("c_fc", "fc1"), ("c_proj", "fc2")):
+                        theirs = theirs.replace(a_, b_)
+                    src = f"encoder.backbone.blocks.{l}.{theirs}"
+                sd[f"decoder.transformer.resblocks.{b}.{part}"] = sd[src].clone()
     if "temporal" in config.train_mode and config.train_mode.temporal == "ranking":
         sd["ranking_transform_param"] = _fill(rng, "proj", (width, 1))
     if config.adapter.type != "none":

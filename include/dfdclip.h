@@ -41,10 +41,15 @@ enum {
   DFD_EPI_QKV_EXPORT,      /* C = acc + bias AND export of the K / V column blocks, CLS row dropped,
                               temporal positional embedding added (clip/model.py:186-199,
                               models.py:505-509, :326-334)                                        */
-  DFD_EPI_RESIDUAL_POS     /* C(c_dtype) += acc + pos[(row / (tokens-1)) % T]: the adapter's second Linear,
+  DFD_EPI_RESIDUAL_POS,    /* C(c_dtype) += acc + pos[(row / (tokens-1)) % T]: the adapter's second Linear,
                               its residual and the decoder's positional add in one pass
                               (models.py:935-937, :326-329); extra.pos may be NULL, extra.tokens-1 =
                               rows (patches) per frame                                            */
+  DFD_EPI_BIAS_GELU        /* C = gelu(acc + bias), gelu(u) = u·Φ(u) = ½u(1 + erf(u/√2)): nn.GELU(), the DINOv2 MLP's
+                              fc1 (dinov2/layers/mlp.py).  dfd_gemm only (f32, or bf16 operands with bf16 / f32 C);
+                              |error| of gelu ≤ 5e-7 before the output rounding.  Appended to the enum without
+                              a new ABI number (no signature or earlier value changed; an existing test pins
+                              17): a library built before it answers DFD_ERR_INVALID_ARG, "unknown epilogue" */
 };
 
 /* Train-mode dropout (models.py:163, :294, :304; adapter :804-912).  Masks are counter-based (Philox4x32-10 on
@@ -383,7 +388,8 @@ int dfd_adapter_bn_apply(const void* y, int y_dtype, const void* residual, void*
 int dfd_adapter_bn_bwd(const void* y, const void* dout, int dout_dtype, void* dy, int dtype, const float* stats,
                        const float* gamma, float* dgamma, float* dbeta, const dfd_dropout_t* drop, void* workspace,
                        int64_t frames, int patches, int width, int T, int train, void* stream);
-/* "768-xxx-768": out = drop(GELU(a)) with nn.GELU()'s exact form 0.5·a·(1 + erf(a/√2)); backward
+/* "768-xxx-768": out = drop(GELU(a)) with nn.GELU()'s erf form 0.5·a·(1 + erf(a/√2)) (the device function
+ * of DFD_EPI_BIAS_GELU); backward
  * da = GELU'(a)·drop(dh) from the saved pre-activation a.  n % 8 == 0, 16-byte aligned; f32 / bf16 in any mix (dh and
  * da share a dtype).  In place allowed where the dtypes agree. */
 int dfd_gelu_erf(const void* a, int a_dtype, void* out, int out_dtype, int64_t n, const dfd_dropout_t* drop, void* stream);
