@@ -6,7 +6,7 @@ raises.  Tensors are passed as raw device pointers; every call enqueues on
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32, c_void_p
 
 import torch
 
@@ -35,6 +35,15 @@ class GemmExtra(Structure):
     _fields_ = [("pos", c_void_p), ("cls", c_void_p), ("k_export", c_void_p), ("v_export", c_void_p),
                 ("tokens", c_int32), ("frames_per_clip", c_int32), ("residual", c_void_p), ("qkv_first", c_int32),
                 ("drop_rng", c_void_p), ("drop_site", c_uint32), ("drop_p", c_float), ("flags", c_uint32)]
+
+
+OPTIM_SGD, OPTIM_ADAMW = 0, 1
+
+
+class OptimExtra(Structure):
+    """dfd_optim_extra: what `dfd_sgd_step` needs beyond SGD's arguments."""
+    _fields_ = [("kind", c_int32), ("reserved", c_int32), ("beta1", c_double), ("beta2", c_double), ("eps", c_double),
+                ("step", c_int64), ("exp_avg_sq", c_void_p)]
 
 
 class DropoutDesc(Structure):
@@ -104,7 +113,7 @@ SIGNATURES = {
     "dfd_linear_rows_bwd_weight": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "dfd_transpose_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "dfd_sgd_blocks": (c_int64, [c_int64, c_int, c_int, c_int]),
-    "dfd_sgd_step": (c_int, [c_void_p, c_int, c_int64, c_float, c_float, c_float, c_int, c_void_p]),
+    "dfd_sgd_step": (c_int, [c_void_p, c_int, c_int64, c_float, c_float, c_float, c_int, c_void_p, POINTER(OptimExtra)]),
     "dfd_layernorm_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                   c_int, c_int, c_float, c_int, c_void_p]),
     "dfd_quickgelu": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, POINTER(DropoutDesc), c_void_p]),
@@ -626,12 +635,21 @@ def sgd_blocks(numel, rows=0, cols=0, mirrored=False):
     return int(load_library().dfd_sgd_blocks(int(numel), int(rows), int(cols), 1 if mirrored else 0))
 
 
-def sgd_step(table, n, total_blocks, lr, momentum, weight_decay, first_step):
-    """`table`: device int64 tensor [n, 7] laid out as dfd_sgd_param (p, g, buf, mirror, numel, rows | cols << 32, first_block)."""
+def adamw_extra(beta1, beta2, eps, step, exp_avg_sq):
+    """The `extra` of an AdamW `sgd_step`: `exp_avg_sq` = device int64 tensor [n] of the second moments' addresses, parallel
+    to the table; `step` = the count after this step (1 on the first)."""
+    _dev(exp_avg_sq)
+    assert exp_avg_sq.dtype == torch.int64 and exp_avg_sq.is_contiguous() and exp_avg_sq.dim() == 1
+    return OptimExtra(OPTIM_ADAMW, 0, float(beta1), float(beta2), float(eps), int(step), exp_avg_sq.data_ptr())
+
+
+def sgd_step(table, n, total_blocks, lr, momentum, weight_decay, first_step, extra=None):
+    """`table`: device int64 tensor [n, 7] laid out as dfd_sgd_param (p, g, buf, mirror, numel, rows | cols << 32, first_block).
+    `extra`: None = SGD; an `OptimExtra` (`adamw_extra`) = AdamW, `buf` then being exp_avg."""
     _dev(table)
     assert table.dtype == torch.int64 and table.is_contiguous() and table.shape == (n, 7)
     _check(load_library().dfd_sgd_step(_ptr(table), int(n), int(total_blocks), float(lr), float(momentum), float(weight_decay),
-                                       1 if first_step else 0, _stream()), "dfd_sgd_step")
+                                       1 if first_step else 0, _stream(), None if extra is None else ctypes.byref(extra)), "dfd_sgd_step")
 
 
 def layernorm_bwd(x, gamma, dy, dx, dgamma, dbeta, xhat_ws, accumulate_dx=False, eps=1e-5):

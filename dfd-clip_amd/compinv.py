@@ -153,5 +153,7 @@ class CompInvEncoder(RuntimeStateMixin, nn.Module):
         return _CompInvLossFn.apply(k, v, b, t, self.adapter.patches)
 
     def configure_optimizers(self, lr):
-        """AdamW over the adapter's parameters (reference `src/models.py:1053-1057`)."""
-        return torch.optim.AdamW(params=self.adapter.parameters(), lr=lr)
+        """AdamW over the adapter's parameters (reference `src/models.py:1053-1057`; torch's default weight decay 0.01): a
+        `torch.optim.AdamW` whose step is one HIP launch (optim.py; CPU parameters are stepped by torch's own code)."""
+        from .optim import FusedAdamW
+        return FusedAdamW(self.adapter.parameters(), lr=lr)

@@ -180,7 +180,7 @@ class Decoder(RuntimeStateMixin, nn.Module):
     def _wt(self, name, w):
         """Transposed [K, N] copy of Linear weight `name`, refreshed when the parameter changed (its
         autograd version counter moves on optimizer.step / load_state_dict / .to()).  The copy keeps its ADDRESS across
-        refreshes (captured graphs read it), and `FusedSGD` rewrites it inside its own launch (`mirrors_written`)."""
+        refreshes (captured graphs read it), and `FusedSGD` / `FusedAdamW` rewrite it inside their own launch (`mirrors_written`)."""
         p = w[name]
         key = (p._version, p.data_ptr(), p.device)
         hit = self._wt_cache.get(name)
@@ -192,7 +192,7 @@ class Decoder(RuntimeStateMixin, nn.Module):
             self._wt_cache[name] = hit = (key, dst)
         return hit[1]
 
-    # ---- transposed copies kept by the optimizer (optim.FusedSGD) -------------------------------------------------
+    # ---- transposed copies kept by the optimizer (optim.FusedSGD / FusedAdamW) ------------------------------------
     _MIRRORED = ("attn.in_proj.weight", "attn.out_proj.weight", "mlp.c_fc.weight", "mlp.c_proj.weight")
 
     def _mirror_names(self):
@@ -214,7 +214,7 @@ class Decoder(RuntimeStateMixin, nn.Module):
         return self._wt(name, {name: p.detach()})
 
     def mirrors_written(self, params):
-        """`FusedSGD` has just rewritten these parameters AND their transposed copies: the copies are current."""
+        """The fused optimizer has just rewritten these parameters AND their transposed copies: the copies are current."""
         names = self._mirror_names()
         for p, mirror in params:
             n = names.get(id(p))
@@ -548,7 +548,7 @@ class Decoder(RuntimeStateMixin, nn.Module):
             # refreshed before every replay, so each step draws new masks and its backward regenerates them
             ent = dict(mask=mask.clone(), bwd={}, rng=None if drop_rng is None else drop_rng.clone())
             self._forward_kernels(w, k_all, v_all, ent["mask"], B, T, P, save=True, drop_rng=ent["rng"], kv_pos=kv_pos)  # eager once: lazy initialisations
-            # the transposed weight copies are NOT nodes of the graph: they sit at fixed addresses, `FusedSGD` rewrites them
+            # the transposed weight copies are NOT nodes of the graph: they sit at fixed addresses, the fused optimizers rewrite them
             # with the weights, and `_refresh_mirrors` (below, before every replay) catches up after anything else
             self._refresh_mirrors(w)
             torch.cuda.synchronize()

@@ -308,13 +308,28 @@ int dfd_linear_rows_bwd_weight(const float* dy, int64_t lddy, const float* x, in
 /* dst[cols, rows] = src[rows, cols]ᵀ — the data gradient of dfd_linear_rows is dfd_linear_rows on Wᵀ. */
 int dfd_transpose_f32(const float* src, float* dst, int rows, int cols, void* stream);
 
-/* One fused step of SGD with momentum and weight decay over a list of f32 parameters — `Detector.configure_optimizers`
- * (reference src/models.py:740-754, stepped once per batch by src/trainer.py:157-177) — in torch.optim.SGD's arithmetic:
- * g = grad + wd p; buf = first_step ? g : momentum buf + g; p -= lr buf.  An entry with `mirror` != NULL is a [rows, cols]
- * weight whose transposed copy [cols, rows] (what dfd_linear_rows_t reads) is rewritten by the same launch.  The table
- * lives in DEVICE memory (the pointers of a model do not change from step to step; lr and momentum do, every step, under
- * OneCycleLR); `first_block` of entry i = sum of dfd_sgd_blocks(...) of the entries before it, `total_blocks` the sum over
- * all. */
+/* One fused optimizer step over a list of f32 parameters — `Detector.configure_optimizers` (reference src/models.py:740-754,
+ * stepped once per batch by src/trainer.py:157-177) and `CompInvEncoder.configure_optimizers` (src/models.py:1053-1057).
+ *
+ * extra == NULL (or kind DFD_OPTIM_SGD): SGD with momentum and weight decay in torch.optim.SGD's arithmetic:
+ *     g = grad + wd p; buf = first_step ? g : momentum buf + g; p -= lr buf.
+ * kind DFD_OPTIM_ADAMW: AdamW in the order of torch.optim.AdamW's multi-tensor path (decoupled weight decay, no amsgrad):
+ *     p *= 1 - lr wd (skipped when wd == 0); m = lerp(m, g, 1 - beta1); v = beta2 v; v += (1 - beta2) g g;
+ *     p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+ * with m = `buf` of the entry (exp_avg) and v = extra->exp_avg_sq[i] for entry i; the bias corrections are formed in double
+ * on the host from `step`, the count AFTER this step (1 on a parameter's first); `momentum` and `first_step` are not read.
+ * Every entry of one call shares one step count.
+ *
+ * An entry with `mirror` != NULL is a [rows, cols] weight whose transposed copy [cols, rows] (what dfd_linear_rows_t reads)
+ * is rewritten by the same launch.  The table lives in DEVICE memory (the pointers of a model do not change from step to
+ * step; lr, momentum and beta1 do, every step, under OneCycleLR); `first_block` of entry i = sum of dfd_sgd_blocks(...) of
+ * the entries before it, `total_blocks` the sum over all.
+ *
+ * `extra` was appended to dfd_sgd_step without a new entry point and WITHOUT a new ABI number: DFD_ABI_VERSION stays 17
+ * (tests/test_adapter_structs_cpu.py pins it).  So dfd_abi_version() does not tell the nine-argument library from the
+ * eight-argument one: a C caller compiled against the earlier header passes no `extra`, the library then reads an
+ * undefined pointer, and the version check does not catch it.  Callers of dfd_sgd_step must be rebuilt against this header
+ * and pass NULL for what the eight-argument form did; the number moves with the next change of the ABI. */
 typedef struct dfd_sgd_param {
   float* p;
   const float* g;
@@ -324,9 +339,17 @@ typedef struct dfd_sgd_param {
   int32_t rows, cols;
   int64_t first_block;
 } dfd_sgd_param;
+enum { DFD_OPTIM_SGD = 0, DFD_OPTIM_ADAMW = 1 };
+typedef struct dfd_optim_extra {
+  int32_t kind;             /* DFD_OPTIM_* */
+  int32_t reserved;         /* 0 */
+  double beta1, beta2, eps; /* doubles, as torch holds them: 1 - beta is formed before the cast to float */
+  int64_t step;
+  float* const* exp_avg_sq; /* DEVICE array of n device pointers, parallel to the table */
+} dfd_optim_extra;
 int64_t dfd_sgd_blocks(int64_t numel, int rows, int cols, int mirrored);
 int dfd_sgd_step(const dfd_sgd_param* table_dev, int n, int64_t total_blocks, float lr, float momentum, float weight_decay,
-                 int first_step, void* stream);
+                 int first_step, void* stream, const dfd_optim_extra* extra);
 
 /* LayerNorm backward over `rows` rows: dx = [dx +] ∂L/∂x (accumulate_dx != 0 adds into dx: the
  * residual branch), dgamma/dbeta [cols] summed over rows; xhat_ws: rows*cols floats of scratch. */
