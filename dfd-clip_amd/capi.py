@@ -137,6 +137,11 @@ SIGNATURES = {
                                      c_void_p, c_void_p, c_void_p]),
 }
 
+# test / measurement hooks outside the ABI header (include/dfdclip_hooks.h)
+HOOK_SIGNATURES = {
+    "dfd_attention_set_variant": (c_int, [c_int]),
+}
+
 _lib = None
 
 
@@ -151,7 +156,7 @@ def load_library(path=None):
     if not os.path.exists(path):
         raise DfdError(f"{path} not found: the HIP kernel library is not built and there is no fallback path")
     lib = ctypes.CDLL(path)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **HOOK_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError:
@@ -386,6 +391,13 @@ def adapter_norm_gelu_bwd(a, dy, da, weight, bias, dweight, dbias, workspace, fr
                                                     _ptr(dweight), _ptr(dbias), _ptr(workspace), frames, patches, x, int(joint),
                                                     eps, _stream()), "dfd_adapter_norm_gelu_bwd")
     return da
+
+
+def attention_set_variant(variant):
+    """0 = default; 1 = the rows kernel stages K and V in 16-key chunks at every token count (bit-identical to the whole-head
+    form); 2 = skip the streaming bf16 MFMA kernel, so the rows kernel serves what it served before.  Per thread.  Returns
+    the previous value."""
+    return load_library().dfd_attention_set_variant(int(variant))
 
 
 def attention_fwd(qkv, out, n_frames, tokens, heads, head_dim=64):

@@ -6,8 +6,13 @@
 //   shapes the MFMA kernel does not take).  One workgroup per (frame, head); K and V of that
 //   head staged once in LDS in their storage dtype; one query row per thread held in
 //   registers; keys streamed from LDS as wave-wide broadcasts; online softmax in fp32.
-// The bf16 MFMA kernel lives in attention_mfma.hip.
+// attn_rows_chunked_kernel: the same arithmetic in the same order per query (attn_row_key), with K and V staged in
+//   key chunks inside the key loop, for token counts whose whole K and V do not fit the 160 KiB of LDS (f32 above 320
+//   tokens, bf16 above 640).  Bit-identical to the whole-head form wherever both can run.
+// The bf16 MFMA kernels live in attention_mfma.hip (193..224 and 257..288 tokens) and attention_mfma_any.hip (the rest
+// from 33 tokens up).
 #include "common.hpp"
+#include "../../include/dfdclip_hooks.h"
 
 namespace {
 
@@ -16,6 +21,40 @@ constexpr int HD = 64;
 template <typename T> struct Vec16;  // 16-byte vector of T
 template <> struct Vec16<float> { using type = f32x4; static constexpr int N = 4; };
 template <> struct Vec16<bf16_t> { using type = bf16x8; static constexpr int N = 8; };
+
+// One key of the online softmax of one query row: q is pre-scaled, Kp / Vp point at the key's 64 channels in LDS.
+template <typename T>
+__device__ __forceinline__ void attn_row_key(const float (&q)[HD], float (&acc)[HD], float& mx, float& l, const T* Kp, const T* Vp) {
+  using V16 = typename Vec16<T>::type;
+  constexpr int VN = Vec16<T>::N;
+  constexpr int CHUNKS = HD / VN;
+  float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+  for (int ch = 0; ch < CHUNKS; ++ch) {
+    const V16 kv = *reinterpret_cast<const V16*>(Kp + ch * VN);
+#pragma unroll
+    for (int e = 0; e < VN; e += 2) {
+      s0 = fmaf(q[ch * VN + e], to_f32(kv[e]), s0);
+      s1 = fmaf(q[ch * VN + e + 1], to_f32(kv[e + 1]), s1);
+    }
+  }
+  const float s = s0 + s1;
+  if (s > mx) {
+    const float alpha = __expf(mx - s);
+    l *= alpha;
+#pragma unroll
+    for (int c = 0; c < HD; ++c) acc[c] *= alpha;
+    mx = s;
+  }
+  const float p = __expf(s - mx);
+  l += p;
+#pragma unroll
+  for (int ch = 0; ch < CHUNKS; ++ch) {
+    const V16 vv = *reinterpret_cast<const V16*>(Vp + ch * VN);
+#pragma unroll
+    for (int e = 0; e < VN; ++e) acc[ch * VN + e] = fmaf(p, to_f32(vv[e]), acc[ch * VN + e]);
+  }
+}
 
 template <typename T>
 __global__ __launch_bounds__(256) void attn_rows_kernel(const T* __restrict__ qkv, int64_t ld_qkv, T* __restrict__ out,
@@ -51,32 +90,7 @@ __global__ __launch_bounds__(256) void attn_rows_kernel(const T* __restrict__ qk
     for (int c = 0; c < HD; ++c) acc[c] = 0.f;
     float mx = -INFINITY, l = 0.f;
     for (int j = 0; j < tokens; ++j) {
-      float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-      for (int ch = 0; ch < CHUNKS; ++ch) {
-        const V16 kv = *reinterpret_cast<const V16*>(Ks + j * HD + ch * VN);
-#pragma unroll
-        for (int e = 0; e < VN; e += 2) {
-          s0 = fmaf(q[ch * VN + e], to_f32(kv[e]), s0);
-          s1 = fmaf(q[ch * VN + e + 1], to_f32(kv[e + 1]), s1);
-        }
-      }
-      const float s = s0 + s1;
-      if (s > mx) {
-        const float alpha = __expf(mx - s);
-        l *= alpha;
-#pragma unroll
-        for (int c = 0; c < HD; ++c) acc[c] *= alpha;
-        mx = s;
-      }
-      const float p = __expf(s - mx);
-      l += p;
-#pragma unroll
-      for (int ch = 0; ch < CHUNKS; ++ch) {
-        const V16 vv = *reinterpret_cast<const V16*>(Vs + j * HD + ch * VN);
-#pragma unroll
-        for (int e = 0; e < VN; ++e) acc[ch * VN + e] = fmaf(p, to_f32(vv[e]), acc[ch * VN + e]);
-      }
+      attn_row_key<T>(q, acc, mx, l, Ks + j * HD, Vs + j * HD);
     }
     const float inv = 1.0f / l;
     T* op = out + ((int64_t)frame * tokens + qi) * ld_out + head * HD;
@@ -90,11 +104,93 @@ __global__ __launch_bounds__(256) void attn_rows_kernel(const T* __restrict__ qk
   }
 }
 
+// K and V in chunks of `chunk` keys: every thread takes part in every refill, also where it has no query row.
+template <typename T>
+__global__ __launch_bounds__(256) void attn_rows_chunked_kernel(const T* __restrict__ qkv, int64_t ld_qkv, T* __restrict__ out,
+                                                                int64_t ld_out, int tokens, int heads, float scale, int chunk) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  T* Ks = reinterpret_cast<T*>(smem_raw);
+  T* Vs = Ks + (size_t)chunk * HD;
+  using V16 = typename Vec16<T>::type;
+  constexpr int VN = Vec16<T>::N;
+  constexpr int CHUNKS = HD / VN;
+  const int frame = blockIdx.x / heads, head = blockIdx.x % heads;
+  const int D = heads * HD;
+  const T* base = qkv + (int64_t)frame * tokens * ld_qkv + head * HD;
+
+  for (int qbase = 0; qbase < tokens; qbase += blockDim.x) {
+    const int qi = qbase + threadIdx.x;
+    const bool live = qi < tokens;
+    float q[HD], acc[HD];
+    const T* qp = base + (int64_t)(live ? qi : tokens - 1) * ld_qkv;
+#pragma unroll
+    for (int ch = 0; ch < CHUNKS; ++ch) {
+      const V16 v = *reinterpret_cast<const V16*>(qp + ch * VN);
+#pragma unroll
+      for (int e = 0; e < VN; ++e) q[ch * VN + e] = to_f32(v[e]) * scale;
+    }
+#pragma unroll
+    for (int c = 0; c < HD; ++c) acc[c] = 0.f;
+    float mx = -INFINITY, l = 0.f;
+    for (int k0 = 0; k0 < tokens; k0 += chunk) {
+      const int nk = min(chunk, tokens - k0);
+      __syncthreads();  // the previous chunk has been consumed
+      for (int c = threadIdx.x; c < nk * CHUNKS; c += blockDim.x) {
+        const int row = c / CHUNKS, ch = c % CHUNKS;
+        const T* src = base + (int64_t)(k0 + row) * ld_qkv + ch * VN;
+        *reinterpret_cast<V16*>(Ks + row * HD + ch * VN) = *reinterpret_cast<const V16*>(src + D);
+        *reinterpret_cast<V16*>(Vs + row * HD + ch * VN) = *reinterpret_cast<const V16*>(src + 2 * D);
+      }
+      __syncthreads();
+      if (live)
+        for (int j = 0; j < nk; ++j) attn_row_key<T>(q, acc, mx, l, Ks + j * HD, Vs + j * HD);
+    }
+    if (live) {
+      const float inv = 1.0f / l;
+      T* op = out + ((int64_t)frame * tokens + qi) * ld_out + head * HD;
+#pragma unroll
+      for (int ch = 0; ch < CHUNKS; ++ch) {
+        V16 o;
+#pragma unroll
+        for (int e = 0; e < VN; ++e) o[e] = from_f32<T>(acc[ch * VN + e] * inv);
+        *reinterpret_cast<V16*>(op + ch * VN) = o;
+      }
+    }
+  }
+}
+
+template <typename T>
+void launch_rows(const void* qkv, int64_t ld_qkv, void* out, int64_t ld_out, int n_frames, int tokens, int heads, float scale,
+                 int chunk, hipStream_t st) {
+  const dim3 grid(n_frames * heads), block(256);
+  if (chunk > 0) {  // chunked staging: at most 64 KiB, two workgroups per CU
+    const size_t lds = (size_t)2 * chunk * HD * sizeof(T);
+    hipLaunchKernelGGL((attn_rows_chunked_kernel<T>), grid, block, lds, st, static_cast<const T*>(qkv), ld_qkv, static_cast<T*>(out),
+                       ld_out, tokens, heads, scale, chunk);
+    return;
+  }
+  const size_t lds = (size_t)2 * tokens * HD * sizeof(T);
+  if (lds > 64 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_rows_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL((attn_rows_kernel<T>), grid, block, lds, st, static_cast<const T*>(qkv), ld_qkv, static_cast<T*>(out), ld_out,
+                     tokens, heads, scale);
+}
+
+thread_local int g_attn_variant = 0;
+
 }  // namespace
+
+// Test hook (include/dfdclip_hooks.h): 0 = default, 1 = force the chunked staging of the rows kernel with 16-key chunks,
+// 2 = skip the streaming MFMA kernel.  Per thread; returns the previous value.
+extern "C" int dfd_attention_set_variant(int variant) {
+  const int old = g_attn_variant;
+  g_attn_variant = variant;
+  return old;
+}
 
 // MFMA kernel (attention_mfma.hip); returns 1 when the shape is not eligible
 int dfd_attention_mfma_try(const void* qkv, int64_t ld_qkv, void* out, int64_t ld_out, int n_frames, int tokens,
-                           int heads, float scale, hipStream_t st);
+                           int heads, float scale, hipStream_t st, int use_any);
 
 extern "C" int dfd_attention_fwd(const void* qkv, int64_t ld_qkv, void* out, int64_t ld_out, int dtype, int n_frames,
                                  int tokens, int heads, int head_dim, float scale, void* stream) {
@@ -106,26 +202,20 @@ extern "C" int dfd_attention_fwd(const void* qkv, int64_t ld_qkv, void* out, int
   DFD_REQUIRE(ld_qkv >= 3 * heads * HD && ld_out >= heads * HD && (ld_qkv * esz) % 16 == 0 && (ld_out * esz) % 16 == 0,
               "dfd_attention_fwd: bad leading dimensions");
   DFD_REQUIRE(dfd_aligned16(qkv) && dfd_aligned16(out), "dfd_attention_fwd: pointers must be 16-byte aligned");
-  const size_t lds = (size_t)2 * tokens * HD * esz;
-  DFD_REQUIRE(lds <= 160 * 1024, "dfd_attention_fwd: tokens=%d needs %zu B of LDS (> 160 KiB)", tokens, lds);
   if (n_frames == 0) return DFD_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
+  const int variant = g_attn_variant;
   if (dtype == DFD_BF16) {
-    const int rc = dfd_attention_mfma_try(qkv, ld_qkv, out, ld_out, n_frames, tokens, heads, scale, st);
+    const int rc = dfd_attention_mfma_try(qkv, ld_qkv, out, ld_out, n_frames, tokens, heads, scale, st, variant != 2);
     if (rc <= 0) return rc;
   }
-  const dim3 grid(n_frames * heads), block(256);
-  if (dtype == DFD_F32) {
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_rows_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((attn_rows_kernel<float>), grid, block, lds, st, static_cast<const float*>(qkv), ld_qkv,
-                       static_cast<float*>(out), ld_out, tokens, heads, scale);
-  } else {
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_rows_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((attn_rows_kernel<bf16_t>), grid, block, lds, st, static_cast<const bf16_t*>(qkv), ld_qkv,
-                       static_cast<bf16_t*>(out), ld_out, tokens, heads, scale);
-  }
+  // whole-head staging wherever K and V of a head fit the 160 KiB of LDS; beyond that, chunks of 64 KiB
+  const size_t lds = (size_t)2 * tokens * HD * esz;
+  const int chunk = variant == 1 ? 16 : lds > 160 * 1024 ? 64 * 1024 / (2 * HD * esz) : 0;
+  if (dtype == DFD_F32)
+    launch_rows<float>(qkv, ld_qkv, out, ld_out, n_frames, tokens, heads, scale, chunk, st);
+  else
+    launch_rows<bf16_t>(qkv, ld_qkv, out, ld_out, n_frames, tokens, heads, scale, chunk, st);
   DFD_CHECK_LAUNCH("dfd_attention_fwd");
   return DFD_OK;
 }

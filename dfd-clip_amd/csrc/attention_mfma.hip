@@ -525,8 +525,12 @@ int launch(const void* qkv, int64_t ld_qkv, void* out, int64_t ld_out, int n_fra
 int dfd_attention_mfma_xrow_try(const void* qkv, int64_t ld_qkv, void* out, int64_t ld_out, int n_frames, int tokens, int heads,
                                 float scale, hipStream_t st);  // attention_mfma_xrow.hip
 
+int dfd_attention_mfma_any_try(const void* qkv, int64_t ld_qkv, void* out, int64_t ld_out, int n_frames, int tokens, int heads,
+                               float scale, hipStream_t st);  // attention_mfma_any.hip
+
+// use_any = 0: token counts outside the two windows are not served (dfd_attention_set_variant(2))
 int dfd_attention_mfma_try(const void* qkv, int64_t ld_qkv, void* out, int64_t ld_out, int n_frames, int tokens, int heads,
-                           float scale, hipStream_t st) {
+                           float scale, hipStream_t st, int use_any) {
   if ((ld_qkv % 8) != 0 || (ld_out % 4) != 0) return 1;
   // NB = ceil(tokens / 32) exactly: the kernels mask only their last key block
   if (tokens > 6 * 32 && tokens <= 7 * 32) {
@@ -542,5 +546,7 @@ int dfd_attention_mfma_try(const void* qkv, int64_t ld_qkv, void* out, int64_t l
     if (rc <= 0) return rc;
     return launch<9>(qkv, ld_qkv, out, ld_out, n_frames, tokens, heads, scale, st);
   }
+  // every other count from 33 up: the streaming kernel (32 and fewer stay on the rows kernel)
+  if (use_any && tokens > 32) return dfd_attention_mfma_any_try(qkv, ld_qkv, out, ld_out, n_frames, tokens, heads, scale, st);
   return 1;
 }

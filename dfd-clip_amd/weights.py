@@ -21,10 +21,12 @@ ARCHS = {
     "ViT-B/16": (224, 16, 768, 12, 12, 512),
     "ViT-B/32": (224, 32, 768, 12, 12, 512),
     "ViT-L/14": (224, 14, 1024, 24, 16, 768),
+    "ViT-L/14@336px": (336, 14, 1024, 24, 16, 768),  # 24x24 patches: 577 tokens
     # test-only shapes: every layout rule of the real model at a fraction of the size
     "tiny": (32, 16, 128, 2, 2, 64),
     "small": (224, 16, 256, 3, 4, 64),
     "small14": (224, 14, 128, 2, 2, 64),  # ViT-L/14's token geometry: 14x14 patches (K = 588), 257 tokens
+    "small24": (336, 14, 128, 2, 2, 64),  # ViT-L/14@336px's token geometry: 24x24 patches (K = 588), 577 tokens
     # DINOv2 towers (`config.foundation == "dinov2"`; dinov2.py): resolution of the RUN, no output projection.  The
     # reference wrapper hard-codes ViT-B/14 (src/models.py:368); `dino_tiny` is the test geometry
     "dinov2_vitb14": (224, 14, 768, 12, 12, 0),
