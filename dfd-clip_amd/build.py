@@ -67,6 +67,7 @@ def build(force=False, verbose=False, extra_flags=()):
     hipcc = _hipcc()
     headers = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".hpp")]
     headers.append(os.path.join(INCLUDE, "dfdclip.h"))
+    headers.append(os.path.join(INCLUDE, "dfdclip_ext.h"))
     jobs, objs = [], []
     for src in sources():
         sp = os.path.join(CSRC, src)

@@ -137,6 +137,16 @@ SIGNATURES = {
                                      c_void_p, c_void_p, c_void_p]),
 }
 
+# entry points appended to the ABI after version 17 without a new number (include/dfdclip_ext.h)
+EXT_SIGNATURES = {
+    "dfd_layernorm_dual": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_float,
+                                   c_float, c_void_p]),
+    "dfd_layernorm2_dual": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
+                                    c_int64, c_int, c_float, c_float, c_void_p]),
+    "dfd_add_layernorm_dual": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64,
+                                       c_void_p, c_int64, c_int64, c_int, c_float, c_float, c_void_p]),
+}
+
 # test / measurement hooks outside the ABI header (include/dfdclip_hooks.h)
 HOOK_SIGNATURES = {
     "dfd_attention_set_variant": (c_int, [c_int]),
@@ -156,7 +166,7 @@ def load_library(path=None):
     if not os.path.exists(path):
         raise DfdError(f"{path} not found: the HIP kernel library is not built and there is no fallback path")
     lib = ctypes.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **HOOK_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **HOOK_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError:
@@ -227,6 +237,47 @@ def add_layernorm(x, delta, gamma, beta, out, eps=1e-5, delta2=None, store_x=Tru
                                             int(bool(store_x)), _ptr(gamma), _ptr(beta), _ptr(out), out.stride(0), _out_dtype(out),
                                             x.shape[0], x.shape[1], eps, float(out_inv_scale), _stream()), "dfd_add_layernorm")
     return out
+
+
+def _dual_outputs(x, out16, out8, out8_inv_scale):
+    assert out16.dtype == torch.bfloat16 and out8.element_size() == 1 and out16.shape == x.shape and out8.shape == x.shape
+    assert out16.stride(1) == 1 and out8.stride(1) == 1 and out8_inv_scale > 0
+
+
+def layernorm_dual(x, gamma, beta, out16, out8, out8_inv_scale, eps=1e-5):
+    """`layernorm` with two outputs from one pass: out16 (bf16) and out8 (e4m3 bytes of the result times `out8_inv_scale`),
+    each bit-identical to the single-output call's."""
+    _dev(x, gamma, beta, out16, out8)
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
+    _dual_outputs(x, out16, out8, out8_inv_scale)
+    _check(load_library().dfd_layernorm_dual(_ptr(x), x.stride(0), _ptr(gamma), _ptr(beta), _ptr(out16), out16.stride(0), _ptr(out8),
+                                             out8.stride(0), x.shape[0], x.shape[1], eps, float(out8_inv_scale), _stream()),
+           "dfd_layernorm_dual")
+    return out16, out8
+
+
+def layernorm2_dual(x, gamma_a, beta_a, gamma_b, beta_b, out16, out8, out8_inv_scale, eps=1e-5):
+    """`layernorm2` with the bf16 and the e4m3 output of LayerNorm_b from one pass."""
+    _dev(x, gamma_a, beta_a, gamma_b, beta_b, out16, out8)
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
+    _dual_outputs(x, out16, out8, out8_inv_scale)
+    _check(load_library().dfd_layernorm2_dual(_ptr(x), x.stride(0), _ptr(gamma_a), _ptr(beta_a), _ptr(gamma_b), _ptr(beta_b), _ptr(out16),
+                                              out16.stride(0), _ptr(out8), out8.stride(0), x.shape[0], x.shape[1], eps,
+                                              float(out8_inv_scale), _stream()), "dfd_layernorm2_dual")
+    return out16, out8
+
+
+def add_layernorm_dual(x, delta, gamma, beta, out16, out8, out8_inv_scale, eps=1e-5, delta2=None, store_x=True):
+    """`add_layernorm` with the bf16 and the e4m3 output from one pass."""
+    _dev(x, delta, gamma, beta, out16, out8, delta2)
+    assert x.dtype == torch.float32 and x.dim() == 2 and delta.shape == x.shape and x.stride(1) == 1 and delta.stride(1) == 1
+    assert delta2 is None or (delta2.dtype == delta.dtype and delta2.shape == x.shape and delta2.stride() == delta.stride())
+    _dual_outputs(x, out16, out8, out8_inv_scale)
+    _check(load_library().dfd_add_layernorm_dual(_ptr(x), x.stride(0), _ptr(delta), _ptr(delta2), delta.stride(0), _DTYPE[delta.dtype],
+                                                 int(bool(store_x)), _ptr(gamma), _ptr(beta), _ptr(out16), out16.stride(0), _ptr(out8),
+                                                 out8.stride(0), x.shape[0], x.shape[1], eps, float(out8_inv_scale), _stream()),
+           "dfd_add_layernorm_dual")
+    return out16, out8
 
 
 def patchify(frames, out, res, patch):

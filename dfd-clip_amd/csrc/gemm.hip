@@ -371,9 +371,9 @@ extern "C" int dfd_gemm_fp8(const void* A, int64_t lda, const void* W, int64_t l
   DFD_REQUIRE(A && W && C && col_scale, "dfd_gemm_fp8: null pointer");
   DFD_REQUIRE(M >= 0 && N > 0 && K > 0, "dfd_gemm_fp8: bad shape M=%lld N=%d K=%d", (long long)M, N, K);
   DFD_REQUIRE(c_dtype == DFD_BF16 || c_dtype == DFD_FP8, "dfd_gemm_fp8: c_dtype=%d", c_dtype);
-  DFD_REQUIRE(epilogue == DFD_EPI_BIAS || epilogue == DFD_EPI_BIAS_QUICKGELU || epilogue == DFD_EPI_QKV_EXPORT,
-              "dfd_gemm_fp8: epilogue %d not served (BIAS, BIAS_QUICKGELU, QKV_EXPORT)", epilogue);
-  DFD_REQUIRE(c_dtype == DFD_BF16 || (epilogue != DFD_EPI_QKV_EXPORT && out_inv_scale > 0.f), "dfd_gemm_fp8: fp8 output needs out_inv_scale > 0 and a plain / QuickGELU epilogue");
+  DFD_REQUIRE(epilogue == DFD_EPI_BIAS || epilogue == DFD_EPI_BIAS_QUICKGELU || epilogue == DFD_EPI_BIAS_GELU || epilogue == DFD_EPI_QKV_EXPORT,
+              "dfd_gemm_fp8: epilogue %d not served (BIAS, BIAS_QUICKGELU, BIAS_GELU, QKV_EXPORT)", epilogue);
+  DFD_REQUIRE(c_dtype == DFD_BF16 || (epilogue != DFD_EPI_QKV_EXPORT && out_inv_scale > 0.f), "dfd_gemm_fp8: fp8 output needs out_inv_scale > 0 and a plain / QuickGELU / GELU epilogue");
   DFD_REQUIRE(lda >= K && ldw >= K && ldc >= N, "dfd_gemm_fp8: leading dimensions");
   GemmArgs a{};
   a.A = A; a.W = W; a.C = C; a.bias = bias; a.col_scale = col_scale; a.out_inv_scale = out_inv_scale;

@@ -1,5 +1,5 @@
 // Persistent 256x256 GEMM with a PING-PONG K loop: the encoder's GEMM since round 3 (bf16 and e4m3 operands; epilogues
-// BIAS, BIAS_QUICKGELU, BIAS_GELU (bf16 operands only), QKV_EXPORT with a bf16 C, e4m3 C for the first two of the fp8 form; reference clip/model.py:186,
+// BIAS, BIAS_QUICKGELU, BIAS_GELU, QKV_EXPORT with a bf16 C, e4m3 C for the first three of the fp8 form; reference clip/model.py:186,
 // :197, :208-212).  gemm256p.hip (round 2) stays as the fallback for the K depths this loop does not serve.
 //
 // gemm256p runs the same software-pipelined instruction stream in all eight waves: the two waves of a SIMD reach their
@@ -54,7 +54,7 @@ constexpr int NB = 2 * (DEPTH - 1);  // requests younger than the unit a segment
 template <int EPI, int RB, bool F8, bool CF8>
 __global__ __launch_bounds__(512) void gemm256e_kernel(const GemmArgs a, int tiles_m, int tiles_n) {
   static_assert(!F8 || RB == 8, "fp8 form: 256-row tiles only");
-  static_assert(!CF8 || (F8 && EPI != DFD_EPI_QKV_EXPORT), "fp8 output: fp8 operands, plain or QuickGELU epilogue");
+  static_assert(!CF8 || (F8 && EPI != DFD_EPI_QKV_EXPORT), "fp8 output: fp8 operands, plain, QuickGELU or GELU epilogue");
   constexpr int ESZ = F8 ? 1 : 2;  // bytes per operand element
   constexpr int CSZ = CF8 ? 1 : 2;  // bytes per output element
   constexpr int TMU = 32 * RB;    // rows a tile uses
@@ -816,7 +816,7 @@ int dfd_gemm256e_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st) {
   }
 }
 
-// fp8 (e4m3) operands on the block-scaled matrix cores; C bf16, or e4m3 for the plain / QuickGELU epilogues
+// fp8 (e4m3) operands on the block-scaled matrix cores; C bf16, or e4m3 for the plain / QuickGELU / GELU epilogues
 int dfd_gemm256e_f8_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st) {
   if (c_dtype != DFD_BF16 && c_dtype != DFD_FP8) return 1;
   if (!a.col_scale || (reinterpret_cast<uintptr_t>(a.col_scale) & 15) != 0) return 1;
@@ -826,6 +826,8 @@ int dfd_gemm256e_f8_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st)
       return c_dtype == DFD_FP8 ? launch256e<DFD_EPI_BIAS, true, true>(a, st) : launch256e<DFD_EPI_BIAS, true, false>(a, st);
     case DFD_EPI_BIAS_QUICKGELU:
       return c_dtype == DFD_FP8 ? launch256e<DFD_EPI_BIAS_QUICKGELU, true, true>(a, st) : launch256e<DFD_EPI_BIAS_QUICKGELU, true, false>(a, st);
+    case DFD_EPI_BIAS_GELU:
+      return c_dtype == DFD_FP8 ? launch256e<DFD_EPI_BIAS_GELU, true, true>(a, st) : launch256e<DFD_EPI_BIAS_GELU, true, false>(a, st);
     case DFD_EPI_QKV_EXPORT: {
       if (c_dtype != DFD_BF16 || check_export_e(a)) return 1;
       GemmArgs b = a;

@@ -17,6 +17,7 @@
 //   * epilogue staging lives in the 32 KB of LDS beside the 128 KB ring (4 KB per wave, 32 rows per pass).
 // Epilogues with a bf16 C: BIAS, BIAS_QUICKGELU, QKV_EXPORT (reference clip/model.py:186, :197, :208-212).
 #include "gemm256p_common.hpp"
+#include "gelu.hpp"
 
 namespace {
 
@@ -36,7 +37,7 @@ namespace {
 template <int EPI, int RB, bool F8, bool CF8>
 __global__ __launch_bounds__(512) void gemm256p_kernel(const GemmArgs a, int tiles_m, int tiles_n) {
   static_assert(!F8 || RB == 8, "fp8 form: 256-row tiles only");
-  static_assert(!CF8 || (F8 && EPI != DFD_EPI_QKV_EXPORT), "fp8 output: fp8 operands, plain or QuickGELU epilogue");
+  static_assert(!CF8 || (F8 && EPI != DFD_EPI_QKV_EXPORT), "fp8 output: fp8 operands, plain, QuickGELU or GELU epilogue");
   constexpr int ESZ = F8 ? 1 : 2;      // bytes per operand element
   constexpr int CSZ = CF8 ? 1 : 2;     // bytes per output element
   constexpr int TMU = 32 * RB;   // rows a tile uses
@@ -442,6 +443,8 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(const GemmArgs a, int til
 #pragma unroll
           for (int e = 0; e < 4; ++e) d[e] = __builtin_amdgcn_rcpf(d[e]);
           v = v * d;
+        } else if constexpr (EPI == DFD_EPI_BIAS_GELU) {
+          v = gelu_erf4(v);  // gelu.hpp: the function gemm256e.hip applies, so the two kernels agree bit for bit
         }
         return v;
       };
@@ -606,7 +609,7 @@ int dfd_gemm256p_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st) {
   }
 }
 
-// fp8 (e4m3) operands on the block-scaled matrix cores; C bf16, or e4m3 for the plain / QuickGELU epilogues
+// fp8 (e4m3) operands on the block-scaled matrix cores; C bf16, or e4m3 for the plain / QuickGELU / GELU epilogues
 int dfd_gemm256p_f8_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st) {
   if (c_dtype != DFD_BF16 && c_dtype != DFD_FP8) return 1;
   if (!a.col_scale || (reinterpret_cast<uintptr_t>(a.col_scale) & 15) != 0) return 1;
@@ -616,6 +619,8 @@ int dfd_gemm256p_f8_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st)
       return c_dtype == DFD_FP8 ? launch256p<DFD_EPI_BIAS, true, true>(a, st) : launch256p<DFD_EPI_BIAS, true, false>(a, st);
     case DFD_EPI_BIAS_QUICKGELU:
       return c_dtype == DFD_FP8 ? launch256p<DFD_EPI_BIAS_QUICKGELU, true, true>(a, st) : launch256p<DFD_EPI_BIAS_QUICKGELU, true, false>(a, st);
+    case DFD_EPI_BIAS_GELU:
+      return c_dtype == DFD_FP8 ? launch256p<DFD_EPI_BIAS_GELU, true, true>(a, st) : launch256p<DFD_EPI_BIAS_GELU, true, false>(a, st);
     case DFD_EPI_QKV_EXPORT: {
       if (c_dtype != DFD_BF16 || check_export(a)) return 1;
       GemmArgs b = a;

@@ -8,6 +8,7 @@
 // dfd_patchify: frames [N,3,R,R] f32 -> patch rows [N*P, kpad] so that the patch conv
 //   (clip/model.py:264, :277) is a plain A·Wᵀ GEMM with W = conv1.weight.view(D, 3*p*p).
 #include "common.hpp"
+#include "../../include/dfdclip_ext.h"
 
 // e4m3 output (the A operand of an fp8 GEMM, dfd_gemm_fp8): stored value = e4m3(y * inv_scale), saturated at +-448
 struct fp8_t {
@@ -32,11 +33,15 @@ __device__ __forceinline__ void store_row4(OutT* p, f32x4 o, float inv_scale) {
   }
 }
 
-template <typename OutT, int SLABS>
+// DUAL (all three row kernels): the row is also written as e4m3 to y8 (row stride ldy8) from the registers that hold the
+// normalised f32 values — OutT is bf16 then, and inv_scale belongs to y8.  A "kv-bf16" layer of the fp8 encoder reads its
+// LayerNorm output in both formats (encoder.py); a second LayerNorm call would read the f32 residual stream once more.
+template <typename OutT, int SLABS, bool DUAL = false>
 __global__ __launch_bounds__(256) void layernorm_rows_kernel(const float* __restrict__ x, int64_t ldx,
                                                              const float* __restrict__ gamma,
                                                              const float* __restrict__ beta, OutT* __restrict__ y,
-                                                             int64_t ldy, int64_t rows, int cols, float eps, float inv_scale) {
+                                                             int64_t ldy, int64_t rows, int cols, float eps, float inv_scale,
+                                                             fp8_t* __restrict__ y8 = nullptr, int64_t ldy8 = 0) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -78,6 +83,7 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const float* __rest
 #pragma unroll
       for (int j = 0; j < 4; ++j) o[j] = (v[i][j] - mean) * rstd * g[j] + b[j];
       store_row4(yr + c, o, inv_scale);
+      if constexpr (DUAL) store_row4(y8 + row * ldy8 + c, o, inv_scale);
     }
   }
 }
@@ -107,11 +113,12 @@ static int launch_ln(const float* x, int64_t ldx, const float* g, const float* b
 // Two LayerNorms back to back over the same rows in one pass: x <- LN_a(x) (f32, in place), y = LN_b(x).  The
 // encoder's ln_pre followed by the first block's ln_1 (clip/model.py:292, :221): the row stays in registers between
 // the two, so x is read once instead of twice.  Same arithmetic, in the same order, as two dfd_layernorm calls.
-template <typename OutT, int SLABS>
+template <typename OutT, int SLABS, bool DUAL = false>
 __global__ __launch_bounds__(256) void layernorm2_rows_kernel(float* __restrict__ x, int64_t ldx, const float* __restrict__ ga,
                                                               const float* __restrict__ ba, const float* __restrict__ gb,
                                                               const float* __restrict__ bb, OutT* __restrict__ y, int64_t ldy,
-                                                              int64_t rows, int cols, float eps, float inv_scale) {
+                                                              int64_t rows, int cols, float eps, float inv_scale,
+                                                              fp8_t* __restrict__ y8 = nullptr, int64_t ldy8 = 0) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -160,6 +167,7 @@ __global__ __launch_bounds__(256) void layernorm2_rows_kernel(float* __restrict_
           v[i] = o;
         } else {
           store_row4(y + row * ldy + c, o, inv_scale);
+          if constexpr (DUAL) store_row4(y8 + row * ldy8 + c, o, inv_scale);
         }
       }
     }
@@ -226,13 +234,14 @@ extern "C" int dfd_layernorm(const float* x, int64_t ldx, const float* gamma, co
 // per wave of tiles with every CU in its epilogue at once), and folds the add into the LayerNorm
 // that follows — exactly torch autocast's dataflow (Linear output in bf16, added to the fp32 stream).
 // Bytes per row: cols * (4 + sizeof(delta) + 4 + sizeof(y)).
-template <typename DeltaT, typename OutT, int SLABS>
+template <typename DeltaT, typename OutT, int SLABS, bool DUAL = false>
 __global__ __launch_bounds__(256) void add_layernorm_rows_kernel(float* __restrict__ x, int64_t ldx,
                                                                  const DeltaT* __restrict__ delta, int64_t ldd,
                                                                  const DeltaT* __restrict__ delta2, int store_x,
                                                                  const float* __restrict__ gamma,
                                                                  const float* __restrict__ beta, OutT* __restrict__ y,
-                                                                 int64_t ldy, int64_t rows, int cols, float eps, float inv_scale) {
+                                                                 int64_t ldy, int64_t rows, int cols, float eps, float inv_scale,
+                                                                 fp8_t* __restrict__ y8 = nullptr, int64_t ldy8 = 0) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -289,6 +298,7 @@ __global__ __launch_bounds__(256) void add_layernorm_rows_kernel(float* __restri
 #pragma unroll
       for (int j = 0; j < 4; ++j) o[j] = (v[i][j] - mean) * rstd * g[j] + b[j];
       store_row4(yr + c, o, inv_scale);
+      if constexpr (DUAL) store_row4(y8 + row * ldy8 + c, o, inv_scale);
     }
   }
 }
@@ -340,6 +350,128 @@ extern "C" int dfd_add_layernorm(float* x, int64_t ldx, const void* delta, const
   if (y_dtype == DFD_F32) return launch_add_ln<bf16_t, float>(x, ldx, delta, ldd, delta2, store_x, gamma, beta, y, ldy, rows, cols, eps, 1.f, st);
   if (y_dtype == DFD_FP8) return launch_add_ln<bf16_t, fp8_t>(x, ldx, delta, ldd, delta2, store_x, gamma, beta, y, ldy, rows, cols, eps, y_inv_scale, st);
   return launch_add_ln<bf16_t, bf16_t>(x, ldx, delta, ldd, delta2, store_x, gamma, beta, y, ldy, rows, cols, eps, 1.f, st);
+}
+
+// ---- dual-output forms: y16 (bf16) and y8 (e4m3 of the same f32 value * y8_inv_scale) in one pass ---------------
+// Each output is bit-identical to what the single-output entry point writes for that type; the restrictions are those
+// of the single-output twin.
+static int dual_args_ok(const char* what, const void* y16, int64_t ldy16, const void* y8, int64_t ldy8, int cols, float y8_inv_scale) {
+  if (!y16 || !y8) {
+    dfd_set_error("%s: null pointer", what);
+    return 0;
+  }
+  if (ldy16 < cols || ldy8 < cols || ldy16 % 4 != 0 || ldy8 % 4 != 0) {
+    dfd_set_error("%s: bad leading dimension (ldy16=%lld ldy8=%lld)", what, (long long)ldy16, (long long)ldy8);
+    return 0;
+  }
+  if (((uintptr_t)y16 & 7) != 0 || ((uintptr_t)y8 & 3) != 0) {
+    dfd_set_error("%s: y16 must be 8-byte and y8 4-byte aligned", what);
+    return 0;
+  }
+  if (!(y8_inv_scale > 0.f)) {
+    dfd_set_error("%s: y8_inv_scale must be > 0", what);
+    return 0;
+  }
+  if (y16 == y8) {
+    dfd_set_error("%s: y16 and y8 must not alias", what);
+    return 0;
+  }
+  return 1;
+}
+
+extern "C" int dfd_layernorm_dual(const float* x, int64_t ldx, const float* gamma, const float* beta, void* y16, int64_t ldy16,
+                                  void* y8, int64_t ldy8, int64_t rows, int cols, float eps, float y8_inv_scale, void* stream) {
+  DFD_REQUIRE(x && gamma && beta, "dfd_layernorm_dual: null pointer");
+  DFD_REQUIRE(rows >= 0 && cols > 0 && cols % 4 == 0 && cols <= 4096, "dfd_layernorm_dual: cols=%d must be a multiple of 4, <= 4096", cols);
+  DFD_REQUIRE(ldx >= cols && ldx % 4 == 0, "dfd_layernorm_dual: bad leading dimension (ldx=%lld)", (long long)ldx);
+  DFD_REQUIRE(dfd_aligned16(x) && dfd_aligned16(gamma) && dfd_aligned16(beta), "dfd_layernorm_dual: pointers must be 16-byte aligned");
+  if (!dual_args_ok("dfd_layernorm_dual", y16, ldy16, y8, ldy8, cols, y8_inv_scale)) return DFD_ERR_INVALID_ARG;
+  DFD_REQUIRE(static_cast<const void*>(x) != y16 && static_cast<const void*>(x) != y8, "dfd_layernorm_dual: an output must not alias x");
+  if (rows == 0) return DFD_OK;
+  const int slabs = (cols + 255) / 256;
+  const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+#define LND_CASE(S)                                                                                                          \
+  case S:                                                                                                                    \
+    hipLaunchKernelGGL((layernorm_rows_kernel<bf16_t, S, true>), grid, block, 0, st, x, ldx, gamma, beta, static_cast<bf16_t*>(y16), \
+                       ldy16, rows, cols, eps, y8_inv_scale, static_cast<fp8_t*>(y8), ldy8);                                 \
+    break;
+  switch (slabs) {
+    LND_CASE(1) LND_CASE(2) LND_CASE(3) LND_CASE(4) LND_CASE(5) LND_CASE(6) LND_CASE(7) LND_CASE(8)
+    LND_CASE(9) LND_CASE(10) LND_CASE(11) LND_CASE(12) LND_CASE(13) LND_CASE(14) LND_CASE(15) LND_CASE(16)
+  }
+#undef LND_CASE
+  DFD_CHECK_LAUNCH("dfd_layernorm_dual");
+  return DFD_OK;
+}
+
+extern "C" int dfd_layernorm2_dual(float* x, int64_t ldx, const float* gamma_a, const float* beta_a, const float* gamma_b,
+                                   const float* beta_b, void* y16, int64_t ldy16, void* y8, int64_t ldy8, int64_t rows, int cols,
+                                   float eps, float y8_inv_scale, void* stream) {
+  DFD_REQUIRE(x && gamma_a && beta_a && gamma_b && beta_b, "dfd_layernorm2_dual: null pointer");
+  DFD_REQUIRE(rows >= 0 && cols > 0 && cols % 4 == 0 && cols <= 2048, "dfd_layernorm2_dual: cols=%d must be a multiple of 4, <= 2048", cols);
+  DFD_REQUIRE(ldx >= cols && ldx % 4 == 0, "dfd_layernorm2_dual: bad leading dimension (ldx=%lld)", (long long)ldx);
+  DFD_REQUIRE(dfd_aligned16(x) && dfd_aligned16(gamma_a) && dfd_aligned16(beta_a) && dfd_aligned16(gamma_b) && dfd_aligned16(beta_b),
+              "dfd_layernorm2_dual: pointers must be 16-byte aligned");
+  if (!dual_args_ok("dfd_layernorm2_dual", y16, ldy16, y8, ldy8, cols, y8_inv_scale)) return DFD_ERR_INVALID_ARG;
+  DFD_REQUIRE(static_cast<void*>(x) != y16 && static_cast<void*>(x) != y8, "dfd_layernorm2_dual: an output must not alias x");
+  if (rows == 0) return DFD_OK;
+  const int slabs = (cols + 255) / 256;
+  const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+#define LN2D_CASE(S)                                                                                                         \
+  case S:                                                                                                                    \
+    hipLaunchKernelGGL((layernorm2_rows_kernel<bf16_t, S, true>), grid, block, 0, st, x, ldx, gamma_a, beta_a, gamma_b, beta_b, \
+                       static_cast<bf16_t*>(y16), ldy16, rows, cols, eps, y8_inv_scale, static_cast<fp8_t*>(y8), ldy8);      \
+    break;
+  switch (slabs) {
+    LN2D_CASE(1) LN2D_CASE(2) LN2D_CASE(3) LN2D_CASE(4) LN2D_CASE(5) LN2D_CASE(6) LN2D_CASE(7) LN2D_CASE(8)
+  }
+#undef LN2D_CASE
+  DFD_CHECK_LAUNCH("dfd_layernorm2_dual");
+  return DFD_OK;
+}
+
+template <typename DeltaT>
+static int launch_add_ln_dual(float* x, int64_t ldx, const void* delta, int64_t ldd, const void* delta2, int store_x, const float* g,
+                              const float* b, void* y16, int64_t ldy16, void* y8, int64_t ldy8, int64_t rows, int cols, float eps,
+                              float inv_scale, hipStream_t st) {
+  const int slabs = (cols + 255) / 256;
+  const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+  const DeltaT* dd = static_cast<const DeltaT*>(delta);
+  const DeltaT* dd2 = static_cast<const DeltaT*>(delta2);
+#define ALND_CASE(S)                                                                                                         \
+  case S:                                                                                                                    \
+    hipLaunchKernelGGL((add_layernorm_rows_kernel<DeltaT, bf16_t, S, true>), grid, block, 0, st, x, ldx, dd, ldd, dd2, store_x, g, b, \
+                       static_cast<bf16_t*>(y16), ldy16, rows, cols, eps, inv_scale, static_cast<fp8_t*>(y8), ldy8);         \
+    break;
+  switch (slabs) {
+    ALND_CASE(1) ALND_CASE(2) ALND_CASE(3) ALND_CASE(4) ALND_CASE(5) ALND_CASE(6) ALND_CASE(7) ALND_CASE(8)
+  }
+#undef ALND_CASE
+  DFD_CHECK_LAUNCH("dfd_add_layernorm_dual");
+  return DFD_OK;
+}
+
+extern "C" int dfd_add_layernorm_dual(float* x, int64_t ldx, const void* delta, const void* delta2, int64_t ldd, int delta_dtype,
+                                      int store_x, const float* gamma, const float* beta, void* y16, int64_t ldy16, void* y8,
+                                      int64_t ldy8, int64_t rows, int cols, float eps, float y8_inv_scale, void* stream) {
+  DFD_REQUIRE(x && delta && gamma && beta, "dfd_add_layernorm_dual: null pointer");
+  DFD_REQUIRE(rows >= 0 && cols > 0 && cols % 4 == 0 && cols <= 2048, "dfd_add_layernorm_dual: cols=%d must be a multiple of 4, <= 2048", cols);
+  DFD_REQUIRE(ldx >= cols && ldd >= cols && ldx % 4 == 0 && ldd % 4 == 0, "dfd_add_layernorm_dual: bad leading dimension (ldx=%lld ldd=%lld)",
+              (long long)ldx, (long long)ldd);
+  DFD_REQUIRE(dfd_aligned16(x) && dfd_aligned16(gamma) && dfd_aligned16(beta) && ((uintptr_t)delta & 7) == 0,
+              "dfd_add_layernorm_dual: pointers must be 16-byte aligned (8 for bf16 operands)");
+  DFD_REQUIRE(delta_dtype == DFD_F32 || delta_dtype == DFD_BF16, "dfd_add_layernorm_dual: delta_dtype=%d", delta_dtype);
+  if (!dual_args_ok("dfd_add_layernorm_dual", y16, ldy16, y8, ldy8, cols, y8_inv_scale)) return DFD_ERR_INVALID_ARG;
+  DFD_REQUIRE(static_cast<const void*>(x) != y16 && static_cast<const void*>(x) != y8 && delta != y16 && delta != y8 && delta2 != y16 && delta2 != y8,
+              "dfd_add_layernorm_dual: an output must not alias x or a delta");
+  DFD_REQUIRE(!delta2 || ((uintptr_t)delta2 & 7) == 0, "dfd_add_layernorm_dual: delta2 must be 8-byte aligned");
+  if (rows == 0) return DFD_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (delta_dtype == DFD_F32)
+    return launch_add_ln_dual<float>(x, ldx, delta, ldd, delta2, store_x, gamma, beta, y16, ldy16, y8, ldy8, rows, cols, eps, y8_inv_scale, st);
+  return launch_add_ln_dual<bf16_t>(x, ldx, delta, ldd, delta2, store_x, gamma, beta, y16, ldy16, y8, ldy8, rows, cols, eps, y8_inv_scale, st);
 }
 
 // ---- patchify -----------------------------------------------------------------------------

@@ -6,7 +6,7 @@ inference loops (`src/trainer.py:147-151`, `src/evaluator.py:80-83`, `inference.
 run unchanged on top of it.  The frozen encoder and the decoder execute in
 libdfdclip_hip.so; PyTorch supplies device memory, streams and the tiny per-sample loss.
 
-    Detector(config, num_frames, accelerator, precision="bf16" | "fp32" | "fp8")
+    Detector(config, num_frames, accelerator, precision="bf16" | "fp32" | "fp8", fp8_policy=None)
 
 `precision` is the only addition to the reference signature: "fp32" is the parity path
 (logits within 1e-3 of the reference's fp32 CPU result), "bf16" the throughput path, "fp8" the bf16 path
@@ -247,9 +247,11 @@ class Detector(RuntimeStateMixin, nn.Module):
     def get_default_config():
         return default_detector_config()
 
-    def __init__(self, config, num_frames, accelerator=None, precision="bf16"):
+    def __init__(self, config, num_frames, accelerator=None, precision="bf16", fp8_policy=None):
         super().__init__()
         assert config.decode_mode in ["stride", "index"]
+        if fp8_policy is not None and precision != "fp8":
+            raise ValueError(f"fp8_policy needs precision='fp8' (got precision={precision!r})")
         capi.load_library()  # fail at construction, not at first forward, when the kernels are missing
         self.config = config
         self.precision = precision
@@ -273,6 +275,8 @@ class Detector(RuntimeStateMixin, nn.Module):
         self.op_mode = config.op_mode
         self.losses = [make_task_loss(spec) for spec in config.losses]
         self.layer_indices = resolve_layer_indices(config, len(self.encoder.transformer.resblocks))
+        if precision == "fp8":
+            self.encoder.set_fp8_policy(fp8_policy, tapped=self.layer_indices)
         self.decoder = Decoder(self, config, num_frames)
         self.adapter = self._build_adapter(config, num_frames)
         self.transform = ClipTransform(self.encoder.input_resolution, mean=self.encoder.pixel_mean, std=self.encoder.pixel_std)
@@ -332,6 +336,14 @@ class Detector(RuntimeStateMixin, nn.Module):
         """fp8 path: fix the encoder's static activation scales from representative clips x [B,T,3,R,R] (or frames
         [N,3,R,R]); see `VisionTransformer.calibrate_fp8`.  Without it the first forward calibrates on its own batch."""
         return self.encoder.calibrate_fp8(x.flatten(0, 1) if x.dim() == 5 else x, margin=margin)
+
+    def set_fp8_policy(self, policy):
+        """fp8 path: which projections of which encoder layer run on e4m3 operands — a preset name or a per-layer list
+        (`encoder.expand_fp8_policy`); "kv-bf16" entries refer to this detector's tapped layers.  Calibration and weights
+        stay; captured encoder graphs are dropped."""
+        plan = self.encoder.set_fp8_policy(policy, tapped=self.layer_indices)
+        self._enc_graphs, self._enc_graph_seen = {}, {}
+        return plan
 
     def seed_dropout(self, seed):
         """Fix the dropout stream: the same seed (and the same number of training forwards since) gives the

@@ -16,7 +16,7 @@ width, so it runs on `VisionTransformer`'s kernel sequence.  What differs, and w
                                     (`interpolate_pos_encoding`), once per staging, with torch
   no ln_pre                         `_stage` leaves its entry None
   LayerNorm eps = 1e-6              `ln_eps`
-  nn.GELU() (erf) in the MLP        `act_epilogue` = DFD_EPI_BIAS_GELU
+  nn.GELU() (erf) in the MLP        `act_epilogue` = DFD_EPI_BIAS_GELU (bf16 and e4m3 operands, bf16 and e4m3 output)
   LayerScale (ls1 / ls2 gamma)      the tower is frozen, so gamma is folded into the Linear before it:
                                     W' = diag(gamma) W, b' = gamma b for attn.proj and mlp.fc2, and the residual
                                     epilogues serve unchanged.  Re-folded whenever the parameters change
@@ -31,7 +31,7 @@ import torch
 from torch import nn
 
 from . import capi
-from .encoder import VisionTransformer, _Holder
+from .encoder import VisionTransformer, _Holder, quantize_rows_e4m3
 from .weights import ARCHS, DINO_IMG_SIZE
 
 CHECKPOINT = "misc/dinov2_vitb14_pretrain.pth"  # where the reference reads it, relative to the working directory
@@ -116,10 +116,10 @@ class DINOv2(VisionTransformer):
 
     def __init__(self, arch="dinov2_vitb14", precision="bf16", checkpoint=CHECKPOINT):
         nn.Module.__init__(self)
-        if precision == "fp8":
-            raise NotImplementedError("precision='fp8' is not built for the DINOv2 foundation (its fc1 output passes through the "
-                                      "erf GELU epilogue, which has no e4m3 form): use 'bf16' or 'fp32'")
         res, patch, width, layers, heads, _ = ARCHS[arch]
+        if precision == "fp8" and width % 256 != 0:
+            raise NotImplementedError(f"precision='fp8' is not built for a DINOv2 tower of width {width}: the fp8 GEMM serves "
+                                      "N % 256 == 0, K % 128 == 0, K >= 256 (include/dfdclip.h); use 'bf16' or 'fp32'")
         self.backbone = _Backbone(DINO_IMG_SIZE[arch], patch, width, layers, heads)
         if checkpoint and os.path.isfile(checkpoint):
             self.backbone.load_state_dict(torch.load(checkpoint, map_location="cpu", weights_only=True))
@@ -165,6 +165,9 @@ class DINOv2(VisionTransformer):
         for i, b in enumerate(f["blocks"]):
             staged = dict(b, idx=i)
             staged.update({k: b[k].to(act).contiguous() for k in ("w_qkv", "w_out", "w_fc", "w_proj")})
+            if self.precision == "fp8":  # per output row, AFTER the LayerScale fold (fc2's rows carry their gamma)
+                for w, w8, sc in (("w_qkv", "w_qkv8", "s_qkv"), ("w_fc", "w_fc8", "s_fc"), ("w_proj", "w_proj8", "s_proj")):
+                    staged[w8], staged[sc] = quantize_rows_e4m3(b[w])
             p["blocks"].append(staged)
         return p
 

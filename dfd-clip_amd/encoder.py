@@ -17,7 +17,9 @@ All arithmetic runs in libdfdclip_hip.so.  Three precisions:
     Activations: LayerNorm writes its output, and c_fc its QuickGELU output, directly as e4m3 with ONE static
     scale per tensor and layer, taken from a calibration batch (`calibrate_fp8`; the first fp8 forward
     calibrates on its own input otherwise): amax / 448, values beyond it saturate.  Accumulation, bias,
-    residual stream, attention, out_proj and the K/V export stay as in the bf16 path.
+    residual stream, attention, out_proj and the K/V export stay as in the bf16 path.  WHICH of the three projections
+    of which layer run on e4m3 is the precision policy (`set_fp8_policy`, `expand_fp8_policy`): the default "all" is the
+    above; the others keep some of them on the bf16 operands, layer by layer.
 
 HBM layout for a batch of N frames (M = N*tokens rows, D = width), all row-major:
   x    [M, D]   f32   residual stream (updated in place by the residual epilogues)
@@ -36,6 +38,67 @@ import torch
 from torch import nn
 
 from . import capi
+
+
+FP8_PRESETS = ("all", "proj-bf16", "kv-bf16", "kv+proj-bf16", "edges-bf16", "none")
+# The fastest preset whose |dAUROC| against bf16 on ViT-L/14 meets the contract's 1e-3, as measured by
+# tools/bench_fp8_policy.py; None = not measured yet / none but "none" meets it.  The default policy
+# stays "all" either way.
+FP8_CONTRACT_POLICY = None
+_ALL = {"qkv": "fp8", "fc": "fp8", "proj": "fp8"}
+_NONE = {"qkv": "bf16", "fc": "bf16", "proj": "bf16"}
+
+
+def expand_fp8_policy(policy, layers, tapped=None):
+    """The per-layer form of a precision policy of the fp8 path: a list of `layers` dicts
+    {"qkv": "fp8" | "bf16" | "kv-bf16", "fc": "fp8" | "bf16", "proj": "fp8" | "bf16"}, normalised.
+
+    `policy`: None (= "all"), a preset name, or such a list (missing keys = "fp8").  `tapped`: the layers whose K/V the
+    decoder reads (None = every layer: the bare encoder returns them all).
+      qkv "kv-bf16": the K and V thirds of the projection — what the decoder reads — on bf16 operands, the Q third on
+                     e4m3.  On an untapped layer it means "fp8"; on the last tapped layer, of which an extraction pass
+                     computes K and V only, it equals "bf16".
+      proj "fp8"     needs fc "fp8": the e4m3 `u` exists only as the output of the fp8 c_fc's epilogue (a bf16-operand GEMM
+                     with an e4m3 output is not built).
+    Presets: "all" (every projection e4m3: the default), "proj-bf16" (c_proj on bf16 operands, reading a bf16 `u` that the
+    fp8 c_fc writes), "kv-bf16" (qkv "kv-bf16" on the tapped layers), "kv+proj-bf16" (both), "edges-bf16" (the first two
+    and the last two layers entirely bf16, the rest "all"), "none" (every projection bf16: the bf16 path's arithmetic)."""
+    tapped = sorted(set(range(layers) if tapped is None else (int(t) for t in tapped)))
+    if any(t < 0 or t >= layers for t in tapped):
+        raise ValueError(f"fp8 policy: tapped layers {tapped} outside 0..{layers - 1}")
+    if policy is None:
+        policy = "all"
+    if isinstance(policy, str):
+        if policy not in FP8_PRESETS:
+            raise ValueError(f"fp8 policy: unknown preset {policy!r} (presets: {', '.join(FP8_PRESETS)})")
+        kv = "kv-bf16" if policy in ("kv-bf16", "kv+proj-bf16") else "fp8"
+        proj = "bf16" if policy in ("proj-bf16", "kv+proj-bf16") else "fp8"
+        edge = set(range(min(2, layers))) | set(range(max(0, layers - 2), layers)) if policy == "edges-bf16" else set()
+        policy = [dict(_NONE) if policy == "none" or l in edge else {"qkv": kv, "fc": "fp8", "proj": proj} for l in range(layers)]
+    policy = list(policy)
+    if len(policy) != layers:
+        raise ValueError(f"fp8 policy: {len(policy)} entries for {layers} layers")
+    out = []
+    for l, ent in enumerate(policy):
+        if not isinstance(ent, dict) or set(ent) - set(_ALL):
+            raise ValueError(f"fp8 policy, layer {l}: expected a dict with keys qkv / fc / proj, got {ent!r}")
+        e = {**_ALL, **ent}
+        if e["qkv"] not in ("fp8", "bf16", "kv-bf16") or e["fc"] not in ("fp8", "bf16") or e["proj"] not in ("fp8", "bf16"):
+            raise ValueError(f"fp8 policy, layer {l}: {ent!r} (qkv: fp8 | bf16 | kv-bf16; fc, proj: fp8 | bf16)")
+        if e["proj"] == "fp8" and e["fc"] != "fp8":
+            raise ValueError(f"fp8 policy, layer {l}: proj 'fp8' requires fc 'fp8' — the e4m3 input of c_proj exists only as the "
+                             "fp8 c_fc's epilogue output")
+        if e["qkv"] == "kv-bf16":
+            e["qkv"] = "fp8" if l not in tapped else ("bf16" if l == tapped[-1] else "kv-bf16")
+        out.append(e)
+    return out
+
+
+def quantize_rows_e4m3(w):
+    """[N, K] weight -> (e4m3 bytes of w / scale_row, scale_row f32 [N]); scale_row = amax_row / 448."""
+    w = w.detach().to(torch.float32)
+    sc = (w.abs().amax(dim=1) / capi.FP8_MAX).clamp_min(1e-12)
+    return (w / sc[:, None]).to(torch.float8_e4m3fn).view(torch.uint8).contiguous(), sc.contiguous()
 
 
 class RuntimeStateMixin:
@@ -156,6 +219,11 @@ class VisionTransformer(RuntimeStateMixin, nn.Module):
         self._fp8_amax = None  # ... the calibrated activation maxima [layers, 3] (host, f32): survive .to() / load_state_dict /
         self._fp8_margin = 1.0  # broadcasts (which only invalidate what is derived from the weights); `fp8_calibration()`
         self._calib = None
+        # ... and which projections run on e4m3 (`set_fp8_policy`): the policy as given, the tapped layers it was given
+        # for, and its per-layer form.  Like the calibration it is not derived from the weights and survives what
+        # invalidates those.
+        self._fp8_policy, self._fp8_tapped = "all", None
+        self._fp8_plan = expand_fp8_policy("all", layers) if precision == "fp8" else None
         # which GEMM outputs are stored non-temporally (capi.gemm stream_out): they are written once and read back only
         # after other traffic has flushed the caches anyway, and keeping them out of L2 leaves the operand panels there
         self.stream_out = {"qkv": True, "out": True, "fc": True, "proj": True}
@@ -210,8 +278,8 @@ class VisionTransformer(RuntimeStateMixin, nn.Module):
             for bp in p["blocks"]:
                 self._block(ws, bp, ws["qkv"][0], M, n)
         finally:
+            self._ws.pop(self._ws_key(n, 1, 99), None)
             self._calib = None
-            self._ws.pop((n, self.precision, 1, 99), None)
         amax = torch.stack(rec).view(len(p["blocks"]), 3).float().cpu()  # one host sync, at calibration time only
         self._fp8_amax, self._fp8_margin, self._fp8 = amax, float(margin), None
         self._fp8_layers()
@@ -226,6 +294,35 @@ class VisionTransformer(RuntimeStateMixin, nn.Module):
         amax = torch.as_tensor(amax, dtype=torch.float32).cpu()
         assert amax.shape == (self.layers, 3)
         self._fp8_amax, self._fp8_margin, self._fp8 = amax, float(margin), None
+
+    def set_fp8_policy(self, policy, tapped=None):
+        """Choose which projections of which layer run on e4m3 operands (`expand_fp8_policy` has the forms and the
+        presets; None / "all" = every one, the default).  `tapped`: the layers whose K/V the decoder reads (`Detector`
+        passes its `layer_indices`).  One calibration serves every policy: it records the bf16 arithmetic.  Only state
+        derived from the policy is dropped (the scale tables a captured graph is guarded by, workspaces of another buffer
+        set); weights and calibration stay."""
+        if self.precision != "fp8":
+            raise ValueError(f"an fp8 policy needs precision='fp8' (this encoder runs {self.precision!r})")
+        plan = expand_fp8_policy(policy, self.layers, tapped)
+        self._fp8_policy = "all" if policy is None else policy
+        self._fp8_tapped = None if tapped is None else tuple(int(t) for t in tapped)
+        self._fp8_plan = plan
+        self._fp8 = None
+        return plan
+
+    def fp8_policy(self):
+        """The per-layer form of the policy in force (a copy), or None off the fp8 path."""
+        return None if self._fp8_plan is None else [dict(e) for e in self._fp8_plan]
+
+    def _fp8_needs(self, M):
+        """(h8, u8, u): which of the e4m3 `h` / `u` and the bf16 `u` a pass over M rows touches under the policy."""
+        if self.precision != "fp8":
+            return (False, False, True)
+        if self._calib is not None or M < capi.FP8_MIN_ROWS:  # the bf16 arithmetic: calibration, chunks below the e4m3 kernel's shape
+            return (False, False, True)
+        plan = self._fp8_plan
+        return (any(e["qkv"] != "bf16" or e["fc"] == "fp8" for e in plan), any(e["proj"] == "fp8" for e in plan),
+                any(e["proj"] == "bf16" for e in plan))
 
     def _fp8_layers(self):
         """Per-layer activation scales x weight-row scales, rebuilt from the calibration whenever the prepared weights are."""
@@ -281,12 +378,7 @@ class VisionTransformer(RuntimeStateMixin, nn.Module):
         f32 = lambda t: t.detach().to(torch.float32).contiguous()
         p = dict(kpad=kpad, w_patch=wp.to(act).contiguous(), cls=f32(self.class_embedding),
                  pos=f32(self.positional_embedding), ln_pre=(f32(self.ln_pre.weight), f32(self.ln_pre.bias)), blocks=[])
-        def q8(w):
-            """[N, K] weight -> (e4m3 bytes of w / scale_row, scale_row f32 [N]); scale_row = amax_row / 448."""
-            w = w.detach().to(torch.float32)
-            sc = (w.abs().amax(dim=1) / capi.FP8_MAX).clamp_min(1e-12)
-            return (w / sc[:, None]).to(torch.float8_e4m3fn).view(torch.uint8).contiguous(), sc.contiguous()
-
+        q8 = quantize_rows_e4m3
         for blk in self.transformer.resblocks:
             if self.precision == "fp8":
                 f8 = dict(zip(("w_qkv8", "s_qkv"), q8(blk.attn.in_proj_weight)))
@@ -302,10 +394,15 @@ class VisionTransformer(RuntimeStateMixin, nn.Module):
                 w_proj=blk.mlp.c_proj.weight.detach().to(act).contiguous(), b_proj=f32(blk.mlp.c_proj.bias)))
         return p
 
+    def _ws_key(self, n, keep_layers, slot):
+        return (n, self.precision, keep_layers, slot, self._fp8_needs(n * self.tokens))
+
     def _workspace(self, n, keep_layers, slot=0):
         """Activation buffers for n frames.  Rows are padded to a multiple of 256 so tiled kernels
-        never read out of bounds; pad rows hold zeros/garbage that is never stored to real rows."""
-        key = (n, self.precision, keep_layers, slot)
+        never read out of bounds; pad rows hold zeros/garbage that is never stored to real rows.
+        The e4m3 `h8` / `u8` and the bf16 `u` exist only where the fp8 policy has a projection that touches them."""
+        key = self._ws_key(n, keep_layers, slot)
+        need_h8, need_u8, need_u = key[-1]
         ws = self._ws.get(key)
         if ws is None:
             dev = self._param_device()
@@ -317,13 +414,14 @@ class VisionTransformer(RuntimeStateMixin, nn.Module):
             kpad = self._prepare()["kpad"]
             ws = dict(
                 x=torch.zeros(Mp, D, device=dev, dtype=torch.float32), h=torch.zeros(Mp, D, device=dev, dtype=act),
-                mix=torch.zeros(Mp, D, device=dev, dtype=act), u=torch.zeros(Mp, 4 * D, device=dev, dtype=act),
+                mix=torch.zeros(Mp, D, device=dev, dtype=act), u=torch.zeros(Mp, 4 * D, device=dev, dtype=act) if need_u else None,
                 patches=torch.zeros(Pp, kpad, device=dev, dtype=act),
                 delta=torch.zeros(Mp, D, device=dev, dtype=act) if self.deferred_residual else None,
                 delta2=torch.zeros(Mp, D, device=dev, dtype=act) if self.deferred_residual else None, pending=0,
                 qkv=[torch.zeros(Mp, 3 * D, device=dev, dtype=act) for _ in range(keep_layers)])
-            if self.precision == "fp8":
+            if need_h8:
                 ws["h8"] = torch.zeros(Mp, D, device=dev, dtype=torch.uint8)
+            if need_u8:
                 ws["u8"] = torch.zeros(Mp, 4 * D, device=dev, dtype=torch.uint8)
             if len(self._ws) > 6:
                 self._ws.clear()
@@ -364,12 +462,15 @@ class VisionTransformer(RuntimeStateMixin, nn.Module):
         # ln_pre is not run here: the first block's ln_1 does it in the same pass over the rows (`_ln`, dfd_layernorm2)
         ws["ln_pre"] = p["ln_pre"]  # None: a tower without one
 
-    def _ln(self, ws, gb, M, store=True, q=None, discard_x=False):
+    def _ln(self, ws, gb, M, store=True, q=None, discard_x=False, dual=False):
         """h = LayerNorm(x).  On the bf16 path the residual branches that have not been added yet
         (`ws["pending"]` of them: out_proj wrote `ws["delta"]`, c_proj `ws["delta2"]`) are folded in first
         inside the same pass over the rows (dfd_add_layernorm).  ln_2 (`store=False`) normalises
-        x + delta without storing it; the next ln_1 adds both deltas and stores x once per block."""
+        x + delta without storing it; the next ln_1 adds both deltas and stores x once per block.
+        `dual` (with `q`): the bf16 `h` AND the e4m3 `h8` from the one pass (a "kv-bf16" layer reads both)."""
         x = ws["x"]
+        if dual:
+            return self._ln_dual(ws, gb, M, q, discard_x)
         h, inv = (ws["h8"], q) if q is not None else (ws["h"], 0.0)  # q: e4m3 output with this inverse scale (fp8 path)
         pend = ws.get("pending", 0)
         pre = ws.pop("ln_pre", None)
@@ -394,6 +495,25 @@ class VisionTransformer(RuntimeStateMixin, nn.Module):
         else:
             capi.add_layernorm(x[:M], ws["delta"][:M], gb[0], gb[1], h[:M], delta2=ws["delta2"][:M] if pend == 2 else None,
                                eps=self.ln_eps, out_inv_scale=inv)
+            ws["pending"] = 0
+
+    def _ln_dual(self, ws, gb, M, inv, discard_x):
+        """`_ln` for an ln_1 whose output is read as bf16 and as e4m3: the dual-output twins of the same kernels."""
+        x, h, h8 = ws["x"], ws["h"], ws["h8"]
+        pend = ws.get("pending", 0)
+        pre = ws.pop("ln_pre", None)
+        if pre is not None:
+            assert pend == 0
+            if self.width <= 2048:
+                capi.layernorm2_dual(x[:M], pre[0], pre[1], gb[0], gb[1], h[:M], h8[:M], inv, eps=self.ln_eps)
+            else:
+                capi.layernorm(x[:M], pre[0], pre[1], x[:M], eps=self.ln_eps)
+                capi.layernorm_dual(x[:M], gb[0], gb[1], h[:M], h8[:M], inv, eps=self.ln_eps)
+        elif pend == 0:
+            capi.layernorm_dual(x[:M], gb[0], gb[1], h[:M], h8[:M], inv, eps=self.ln_eps)
+        else:
+            capi.add_layernorm_dual(x[:M], ws["delta"][:M], gb[0], gb[1], h[:M], h8[:M], inv, eps=self.ln_eps,
+                                    delta2=ws["delta2"][:M] if pend == 2 else None, store_x=not discard_x)
             ws["pending"] = 0
 
     def _residual(self, ws, a, w, b, M, spare_cus=0, spare_if_free=False):
@@ -426,6 +546,7 @@ class VisionTransformer(RuntimeStateMixin, nn.Module):
         # fp8: chunks below the e4m3 kernel's smallest shape (1024 rows: 6 frames of ViT-B/16, 4 of ViT-L/14 — `ema_frame`
         # batches, a short last clip) run the block on the bf16 operands that calibration keeps anyway
         f8 = self._fp8_layers()[bp["idx"]] if self.precision == "fp8" and calib is None and M >= capi.FP8_MIN_ROWS else None
+        pl = self._fp8_plan[bp["idx"]] if f8 is not None else _NONE  # which of this layer's projections run on e4m3
         so = self.stream_out
         sp = self.spare_cus if (self.spare_layers <= 0 or bp["idx"] < self.spare_layers) else 0
         sp_all = self.spare_cus if bp["idx"] < self.spare_window_layers else 0
@@ -441,9 +562,16 @@ class VisionTransformer(RuntimeStateMixin, nn.Module):
         kw = dict(m=M, tokens=self.tokens, qkv_first=first, stream_out=so["qkv"], spare_cus=sp_qkv, spare_if_free=free)
         if export is not None:
             kw.update(pos=export[2], k_export=export[0], v_export=export[1], frames_per_clip=export[3])
-        if f8 is not None:
+        if pl["qkv"] == "fp8":
             self._ln(ws, bp["ln1"], M, q=f8["h1_inv"], discard_x=kv_only)
             capi.gemm_fp8(ws["h8"], bp["w_qkv8"][rows], qkv[:, rows], f8["cs_qkv"][rows], bp["b_qkv"][rows], capi.EPI_QKV_EXPORT, **kw)
+        elif pl["qkv"] == "kv-bf16" and not kv_only:
+            # the K and V thirds, which the decoder reads, from the bf16 `h` (the call of a last tapped layer); the Q third
+            # from the e4m3 `h8` the same LayerNorm pass wrote
+            self._ln(ws, bp["ln1"], M, q=f8["h1_inv"], dual=True)
+            capi.gemm_fp8(ws["h8"], bp["w_qkv8"][:D], qkv[:, :D], f8["cs_qkv"][:D], bp["b_qkv"][:D], capi.EPI_BIAS, m=M,
+                          stream_out=so["qkv"], spare_cus=sp_qkv, spare_if_free=free)
+            capi.gemm(ws["h"], bp["w_qkv"][D:], qkv[:, D:], bp["b_qkv"][D:], capi.EPI_QKV_EXPORT, **dict(kw, qkv_first=1))
         else:
             self._ln(ws, bp["ln1"], M, discard_x=kv_only and calib is None)
             if calib is not None:
@@ -453,9 +581,15 @@ class VisionTransformer(RuntimeStateMixin, nn.Module):
             return
         capi.attention_fwd(qkv, ws["mix"], n, self.tokens, self.heads)
         self._residual(ws, ws["mix"], bp["w_out"], bp["b_out"], M, spare_cus=sp_out, spare_if_free=free)
-        if f8 is not None:
+        if pl["fc"] == "fp8" and pl["proj"] == "bf16":
+            # c_fc on e4m3 operands with a bf16 `u`, which c_proj reads as the bf16 path does
             self._ln(ws, bp["ln2"], M, store=False, q=f8["h2_inv"])
-            capi.gemm_fp8(ws["h8"], bp["w_fc8"], ws["u8"], f8["cs_fc"], bp["b_fc"], capi.EPI_BIAS_QUICKGELU, m=M,
+            capi.gemm_fp8(ws["h8"], bp["w_fc8"], ws["u"], f8["cs_fc"], bp["b_fc"], self.act_epilogue, m=M,
+                          stream_out=so["fc"], spare_cus=sp_fc, spare_if_free=free)
+            self._residual(ws, ws["u"], bp["w_proj"], bp["b_proj"], M, spare_cus=sp_proj, spare_if_free=free)
+        elif pl["fc"] == "fp8":
+            self._ln(ws, bp["ln2"], M, store=False, q=f8["h2_inv"])
+            capi.gemm_fp8(ws["h8"], bp["w_fc8"], ws["u8"], f8["cs_fc"], bp["b_fc"], self.act_epilogue, m=M,
                           out_inv_scale=f8["u_inv"], stream_out=so["fc"], spare_cus=sp_fc, spare_if_free=free)
             pend = ws.get("pending", 0)  # c_proj: the second deferred residual of the block (see `_residual`)
             capi.gemm_fp8(ws["u8"], bp["w_proj8"], ws["delta2" if pend else "delta"], f8["cs_proj"], bp["b_proj"], capi.EPI_BIAS, m=M,

@@ -31,10 +31,11 @@ ARCHS = {
     # reference wrapper hard-codes ViT-B/14 (src/models.py:368); `dino_tiny` is the test geometry
     "dinov2_vitb14": (224, 14, 768, 12, 12, 0),
     "dino_tiny": (28, 14, 128, 2, 2, 0),
+    "dino_w768": (28, 14, 768, 2, 12, 0),  # dino_tiny's 5 tokens per frame at a width the fp8 GEMM serves (K % 256 == 0, K >= 768)
 }
-# ... and the image size their `pos_embed` is stored for (518 px = a 37x37 grid, resampled to the run's grid; the tiny
-# one 70 px = 5x5 -> 2x2)
-DINO_IMG_SIZE = {"dinov2_vitb14": 518, "dino_tiny": 70}
+# ... and the image size their `pos_embed` is stored for (518 px = a 37x37 grid, resampled to the run's grid; the test
+# geometries 70 px = 5x5 -> 2x2)
+DINO_IMG_SIZE = {"dinov2_vitb14": 518, "dino_tiny": 70, "dino_w768": 70}
 
 
 # the model names the reference's `clip.load` knows (src/clip/clip.py:30-40): what a reference config carries in `architecture`

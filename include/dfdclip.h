@@ -46,8 +46,8 @@ enum {
                               (models.py:935-937, :326-329); extra.pos may be NULL, extra.tokens-1 =
                               rows (patches) per frame                                            */
   DFD_EPI_BIAS_GELU        /* C = gelu(acc + bias), gelu(u) = u·Φ(u) = ½u(1 + erf(u/√2)): nn.GELU(), the DINOv2 MLP's
-                              fc1 (dinov2/layers/mlp.py).  dfd_gemm only (f32, or bf16 operands with bf16 / f32 C);
-                              |error| of gelu ≤ 5e-7 before the output rounding.  Appended to the enum without
+                              fc1 (dinov2/layers/mlp.py).  dfd_gemm (f32, or bf16 operands with bf16 / f32 C) and
+                              dfd_gemm_fp8 (bf16 or e4m3 C); |error| of gelu ≤ 5e-7 before the output rounding.  Appended to the enum without
                               a new ABI number (no signature or earlier value changed; an existing test pins
                               17): a library built before it answers DFD_ERR_INVALID_ARG, "unknown epilogue" */
 };
@@ -127,6 +127,8 @@ int dfd_add_layernorm(float* x, int64_t ldx, const void* delta, const void* delt
                       int store_x, const float* gamma, const float* beta, void* y, int64_t ldy, int y_dtype, int64_t rows,
                       int cols, float eps, float y_inv_scale, void* stream);
 
+/* Dual-output forms (bf16 AND e4m3 from one pass) of the three LayerNorm entry points above: include/dfdclip_ext.h. */
+
 /* Frames [n_frames, 3, res, res] (f32) -> patch rows [n_frames*P, kpad] in out_dtype, column
  * k = c*patch*patch + i*patch + j (the flatten order of conv1.weight [D,3,patch,patch]), columns
  * >= 3*patch*patch zero-filled.  The patch conv (clip/model.py:264, :277) then is a plain GEMM. */
@@ -158,8 +160,8 @@ int dfd_gemm(const void* A, int64_t lda, const void* W, int64_t ldw, int ab_dtyp
 /* The same product on OCP e4m3 ("fp8") operands, on the block-scaled matrix cores (v_mfma_scale_f32_16x16x128_f8f6f4,
  * unit block scales; twice the bf16 rate): C = epilogue((A[M,K] · W[N,K]ᵀ) · col_scale[n] + bias[n]).  A, W: one byte per
  * element, row-major (lda, ldw in elements); col_scale[n] = (scale the activations were divided by) x (scale row n of W was
- * divided by); C bf16, or — plain and QuickGELU epilogues — e4m3 of result * out_inv_scale, saturated at +-448 (the c_fc
- * output feeding the next fp8 GEMM).  Epilogues: BIAS, BIAS_QUICKGELU, QKV_EXPORT (exports bf16).  Served shapes:
+ * divided by); C bf16, or — plain, QuickGELU and GELU epilogues — e4m3 of result * out_inv_scale, saturated at +-448 (the c_fc
+ * output feeding the next fp8 GEMM).  Epilogues: BIAS, BIAS_QUICKGELU, BIAS_GELU, QKV_EXPORT (exports bf16).  Served shapes:
  * M >= 1024, N % 256 == 0, K % 128 == 0, K >= 256, 16-byte aligned rows; anything else is DFD_ERR_INVALID_ARG (there is
  * no second fp8 kernel).  BASELINE configs[4]; quantisation policy: dfd-clip_amd/encoder.py. */
 int dfd_gemm_fp8(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, int c_dtype,
