@@ -327,6 +327,20 @@ extern "C" int dfd_gemm_set_variant(int variant) {
   return old;
 }
 
+// The two persistent kernels in their order: gemm256e.hip (ping-pong K loop: K / step even and >= 6), then gemm256p.hip
+// (the other depths; variant 1 goes there at once).  0 = launched (*path = 257 / 256), <0 = error, 1 = neither serves it.
+static int try_persistent_kernels(GemmArgs& a, int c_dtype, int epilogue, bool f8, hipStream_t st, int* path) {
+  // a q|k|v projection without an export is a plain biased store
+  const int epi_p = epilogue == DFD_EPI_QKV_EXPORT && a.k_export == nullptr ? DFD_EPI_BIAS : epilogue;
+  a.no_dynamic = g_gemm_variant != 3;
+  int rc = g_gemm_variant == 1 ? 1 : (f8 ? dfd_gemm256e_f8_try : dfd_gemm256e_try)(a, c_dtype, epi_p, st);
+  *path = 257;
+  if (rc != 1) return rc;
+  rc = (f8 ? dfd_gemm256p_f8_try : dfd_gemm256p_try)(a, c_dtype, epi_p, st);
+  *path = 256;
+  return rc;
+}
+
 extern "C" int dfd_gemm(const void* A, int64_t lda, const void* W, int64_t ldw, int ab_dtype, void* C, int64_t ldc,
                         int c_dtype, const float* bias, int epilogue, const dfd_gemm_extra* extra, int64_t M, int N,
                         int K, void* stream) {
@@ -346,14 +360,9 @@ extern "C" int dfd_gemm(const void* A, int64_t lda, const void* W, int64_t ldw, 
   if (M == 0) return DFD_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (ab_dtype == DFD_BF16) {
-    // a q|k|v projection without an export is a plain biased store
-    const int epi_p = epilogue == DFD_EPI_QKV_EXPORT && a.k_export == nullptr ? DFD_EPI_BIAS : epilogue;
-    a.no_dynamic = g_gemm_variant != 3;
-    int rc = g_gemm_variant == 1 ? 1 : dfd_gemm256e_try(a, c_dtype, epi_p, st);  // ping-pong K loop (K a multiple of 128, >= 384)
-    if (rc == 0) g_last_path = 257;
-    if (rc <= 0) return rc;
-    rc = dfd_gemm256p_try(a, c_dtype, epi_p, st);
-    if (rc == 0) g_last_path = 256;
+    int path = 0;
+    int rc = try_persistent_kernels(a, c_dtype, epilogue, false, st, &path);
+    if (rc == 0) g_last_path = path;
     if (rc <= 0) return rc;
     rc = dfd_gemm256_try(a, c_dtype, epilogue, st);
     if (rc == 0) g_last_path = 256;
@@ -380,10 +389,8 @@ extern "C" int dfd_gemm_fp8(const void* A, int64_t lda, const void* W, int64_t l
   a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.M = M; a.N = N; a.K = K;
   { const int rc = fill_extra(a, epilogue, extra, c_dtype, ldc, M, N); if (rc != DFD_OK) return rc; }
   if (M == 0) return DFD_OK;
-  const int epi_p = epilogue == DFD_EPI_QKV_EXPORT && a.k_export == nullptr ? DFD_EPI_BIAS : epilogue;
-  a.no_dynamic = g_gemm_variant != 3;
-  int rc = g_gemm_variant == 1 ? 1 : dfd_gemm256e_f8_try(a, c_dtype, epi_p, static_cast<hipStream_t>(stream));
-  if (rc == 1) rc = dfd_gemm256p_f8_try(a, c_dtype, epi_p, static_cast<hipStream_t>(stream));
+  int path = 0;  // (dfd_gemm_last_path reports dfd_gemm's launches only)
+  const int rc = try_persistent_kernels(a, c_dtype, epilogue, true, static_cast<hipStream_t>(stream), &path);
   if (rc == 1) {
     dfd_set_error("dfd_gemm_fp8: shape not served (needs M >= 1024, N %% 256 == 0, K %% 128 == 0, K >= 256, 16-byte aligned rows; got M=%lld N=%d K=%d)",
                   (long long)M, N, K);

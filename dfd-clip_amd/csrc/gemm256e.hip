@@ -43,7 +43,6 @@
 #include <unordered_map>
 
 #include "gemm256p_common.hpp"
-#include "gelu.hpp"
 
 namespace {
 
@@ -56,7 +55,6 @@ __global__ __launch_bounds__(512) void gemm256e_kernel(const GemmArgs a, int til
   static_assert(!F8 || RB == 8, "fp8 form: 256-row tiles only");
   static_assert(!CF8 || (F8 && EPI != DFD_EPI_QKV_EXPORT), "fp8 output: fp8 operands, plain, QuickGELU or GELU epilogue");
   constexpr int ESZ = F8 ? 1 : 2;  // bytes per operand element
-  constexpr int CSZ = CF8 ? 1 : 2;  // bytes per output element
   constexpr int TMU = 32 * RB;    // rows a tile uses
   constexpr int WROWS = 16 * RB;  // rows per wave
   constexpr int HB = RB - 4;      // row blocks in the second half
@@ -70,19 +68,13 @@ __global__ __launch_bounds__(512) void gemm256e_kernel(const GemmArgs a, int til
   const int wr = wave >> 2, wc = wave & 3;
   const int ntiles = tiles_m * tiles_n;
 
-  // XCD-aware, bijective position of this workgroup inside one round of the grid (blocks b and b+8 share an XCD)
   const int G = gridDim.x, bid = blockIdx.x;
   const int xcd = bid & 7, q8 = G >> 3, r8 = G & 7;
-  const int pos = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int pos = xcd_position();
 
-  const __amdgpu_buffer_rsrc_t srdA = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.A), 0, (int)(uint32_t)(a.M * a.lda * ESZ), 0x00020000);
-  const __amdgpu_buffer_rsrc_t srdW = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.W), 0, (int)(uint32_t)((int64_t)a.N * a.ldw * ESZ), 0x00020000);
-  const __amdgpu_buffer_rsrc_t srdC = __builtin_amdgcn_make_buffer_rsrc(a.C, 0, (int)(uint32_t)(a.M * a.ldc * CSZ), 0x00020000);
+  const OperandSrds<F8, CF8> srd(a);
+  const __amdgpu_buffer_rsrc_t srdA = srd.A, srdW = srd.W, srdC = srd.C;
   // descriptors of the column vectors as four plain words: their loads are inline asm
-  auto words = [](const float* p, int bytes) {
-    const uint64_t u = reinterpret_cast<uint64_t>(p);
-    return v4i{(int)(uint32_t)u, (int)((uint32_t)(u >> 32) & 0xffffu), bytes, 0x00020000};
-  };
   const v4i srdB = words(a.bias ? a.bias : reinterpret_cast<const float*>(a.W), a.bias ? a.N * 4 : 0);
   [[maybe_unused]] const v4i srdS = words(F8 ? a.col_scale : reinterpret_cast<const float*>(a.W), F8 ? a.N * 4 : 0);
   // dynamic hand-out: this label's workgroups (cnt_x of them, at positions off_x .. of every round) share counter xcd
@@ -214,16 +206,6 @@ __global__ __launch_bounds__(512) void gemm256e_kernel(const GemmArgs a, int til
 
   [[maybe_unused]] unsigned char* const ep = smem + RING + wave * STAGE;
   const int D = EPI == DFD_EPI_QKV_EXPORT ? a.N / (3 - a.qkv_first) : 0;
-  [[maybe_unused]] __amdgpu_buffer_rsrc_t srdK = srdC, srdV = srdC, srdP = srdC;
-  if constexpr (EPI == DFD_EPI_QKV_EXPORT) {
-    if (a.k_export != nullptr) {
-      srdP = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.pos ? a.pos : reinterpret_cast<const float*>(a.W)), 0,
-                                               a.pos ? a.frames_per_clip * D * 4 : 0, 0x00020000);
-      const int64_t erows = (a.M / a.tokens) * (a.tokens - 1);
-      srdK = __builtin_amdgcn_make_buffer_rsrc(a.k_export, 0, (int)(uint32_t)(erows * D * 2), 0x00020000);
-      srdV = __builtin_amdgcn_make_buffer_rsrc(a.v_export, 0, (int)(uint32_t)(erows * D * 2), 0x00020000);
-    }
-  }
 
   const int nk_ = a.K / (F8 ? 128 : TK);
   // (the short-K form needs the next tile before a draw could return; the e4m3 forms have no register left for the draw)
@@ -400,251 +382,19 @@ __global__ __launch_bounds__(512) void gemm256e_kernel(const GemmArgs a, int til
       ktile(nk - 1, C1{}, C2{}, C0{});
     }
 
-    // ---- epilogue (gemm256p.hip's: bias, activation, LDS-staged whole-line stores, left in flight) -------------------
-    // Every address below is rebuilt from an opaque copy of the lane id (left to itself the compiler hoists two dozen
-    // tile-invariant address registers out of the tile loop and spills them).
-    int le = lane;
-    asm volatile("" : "+v"(le));
-    const int er = le & 15, eq = le >> 4;          // accumulator fragment: row er of a 16-row block, columns 4*eq ..
-    const int drow = le >> 3, dc = le & 7;         // drain: row drow of an 8-row group, 16-byte chunk dc
-    const int nb = cur.n0 + wc * 64;
-    const int64_t mrow0 = (int64_t)cur.m0 + wr * WROWS + drow;  // first row this lane stores
-    const int rows_left = (int)min((int64_t)0x7fffffff, a.M - mrow0);
-    int which = 0;
-    if constexpr (EPI == DFD_EPI_QKV_EXPORT) which = cur.n0 / D + a.qkv_first;  // 0 = q, 1 = k, 2 = v
-    const bool exporting = EPI == DFD_EPI_QKV_EXPORT && which > 0 && a.k_export != nullptr;
-    int stores = 2 * RB;
-    {
-      // (column scale and) bias once, in place: both copies of an exported tile read the same registers
-      f32x4 b4[4];
-      [[maybe_unused]] f32x4 cs4[4];
+    // ---- epilogue: the column vectors back from their LDS line as per-fragment vectors, then the shared tile_epilogue ----
+    f32x4 b4[4];
+    [[maybe_unused]] f32x4 cs4[4];
+    const int le = opaque_lane();
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        b4[j] = *reinterpret_cast<const f32x4*>(ep + (j * 16 + eq * 4) * 4);
-        if constexpr (F8) cs4[j] = *reinterpret_cast<const f32x4*>(ep + 256 + (j * 16 + eq * 4) * 4);
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // before the staging below overwrites them
-#pragma unroll
-      for (int i = 0; i < RB; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if constexpr (F8) acc[i][j] = acc[i][j] * cs4[j] + b4[j];
-          else acc[i][j] += b4[j];
-        }
-      if constexpr (EPI == DFD_EPI_QKV_EXPORT) {
-        if (exporting) {
-          // Exported copy of a K / V tile FIRST (its positional-embedding loads then wait only for loads, never for
-          // this tile's stores): bf16(acc + bias + pos[frame % T]) -> row frame*(tokens-1) + token-1 of the export,
-          // the CLS row dropped.  Eight sub-passes of 16 rows parked as f32 (4 KB); the drain adds the embedding
-          // (two 16-byte loads per store, requested at the top of the sub-pass) and rounds once.
-          stores = 4 * RB;
-          const int ecol = nb - (which - a.qkv_first) * D + dc * 8;  // first of this lane's 8 export columns
-          unsigned char* const parkf = ep + er * 256;                 // unit (j*4 + eq) ^ er of a 256-byte row
-          const __amdgpu_buffer_rsrc_t srdE = which == 2 ? srdV : srdK;
-#pragma unroll
-          for (int i = 0; i < RB; ++i) {
-            __builtin_amdgcn_sched_barrier(0);  // keep each sub-pass's embedding loads inside it (16 registers, not 128)
-            uint32_t eoff[2];
-            f32x4 pe[2][2];
-#pragma unroll
-            for (int rr = 0; rr < 2; ++rr) {
-              const int rloc = i * 16 + rr * 8;
-              const uint32_t m = (uint32_t)min(mrow0 + rloc, a.M - 1);
-              const uint32_t frame = a.div_tokens.div(m);
-              const uint32_t tok = m - frame * (uint32_t)a.tokens;
-              const uint32_t t = frame - a.div_frames.div(frame) * (uint32_t)a.frames_per_clip;
-              eoff[rr] = (rloc < rows_left && tok > 0) ? ((frame * (uint32_t)(a.tokens - 1) + tok - 1) * (uint32_t)D + ecol) * 2 : 0xffffffffu;
-              // no embedding (the raw export an adapter reads): add zeros, and issue no load — a register load beside
-              // LDS-DMA costs a vmcnt(0) at its use, i.e. one memory round trip per sub-pass
-              pe[rr][0] = pe[rr][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-              if (a.pos != nullptr) {
-                const uint32_t poff = (t * (uint32_t)D + ecol) * 4;
-                pe[rr][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdP, poff, 0, 0));
-                pe[rr][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdP, poff, 16, 0));
-              }
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-              *reinterpret_cast<f32x4*>(parkf + (((j * 4 + eq) ^ er) << 4)) = acc[i][j];
-#pragma unroll
-            for (int rr = 0; rr < 2; ++rr) {
-              const int row = rr * 8 + drow;
-              const f32x4 x0 = *reinterpret_cast<const f32x4*>(ep + row * 256 + (((2 * dc) ^ row) << 4)) + pe[rr][0];
-              const f32x4 x1 = *reinterpret_cast<const f32x4*>(ep + row * 256 + (((2 * dc + 1) ^ row) << 4)) + pe[rr][1];
-              bf16x8 o;
-#pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                o[e] = (bf16_t)x0[e];
-                o[4 + e] = (bf16_t)x1[e];
-              }
-              store_out(__builtin_bit_cast(v4i, o), srdE, eoff[rr], a.stream_out);
-            }
-          }
-        }
-      }
-      // QuickGELU on a 4-wide fragment (packed f32 arithmetic: gemm256.hip)
-      auto activate = [&](f32x4 v) {
-        if constexpr (EPI == DFD_EPI_BIAS_QUICKGELU) {
-          float cgelu = DFD_QUICKGELU_SCALE;  // opaque + in an SGPR so that the multiply packs
-          asm volatile("" : "+s"(cgelu));
-          const f32x4 t = v * cgelu;
-          f32x4 d;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) d[e] = __builtin_amdgcn_exp2f(t[e]);
-          d = d + 1.0f;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) d[e] = __builtin_amdgcn_rcpf(d[e]);
-          v = v * d;
-        } else if constexpr (EPI == DFD_EPI_BIAS_GELU) {
-          // exact-erf GELU (gelu.hpp): the same scalar function as the general kernel, so the two agree bit for bit
-          v = gelu_erf4(v);
-        }
-        return v;
-      };
-      if constexpr (EPI == DFD_EPI_RESIDUAL_POS) {
-        // C(bf16) = residual + dropout(acc) + pos[(row / rows_per_frame) % T], rounded ONCE (the adapter's second Linear,
-        // reference models.py:795-875, :930-940; gemm256.hip has the one-workgroup-per-tile form of the same arithmetic).
-        // RB sub-passes of 16 rows parked as f32 (4 KB); the drain reads the residual row segment and the positional
-        // embedding (requested at the top of the sub-pass), adds and rounds; 2 stores of 8 rows x 128 B per sub-pass.
-        unsigned char* const parkf = ep + er * 256;  // unit (j*4 + eq) ^ er of a 256-byte row
-        const uint32_t cbase = (uint32_t)((mrow0 * a.ldc + nb + dc * 8) * 2);
-        // The residual and the embedding of sub-pass i + 1 are requested before sub-pass i is drained (one sub-pass of
-        // loads always in flight: with each load waited for where it is issued the epilogue is a chain of 2 RB memory
-        // round trips, 29 us per tile).  Inline-asm loads, counted by hand like the K loop's: queue at the wait of sub-pass
-        // i = [loads i][2 stores of i-1][6 loads of i+1].
-        const v4i srdRw = a.residual ? words(reinterpret_cast<const float*>(a.residual), (int)(uint32_t)(a.M * a.ldc * 2))
-                                     : words(reinterpret_cast<const float*>(a.C), (int)(uint32_t)(a.M * a.ldc * 2));
-        const v4i srdQw = words(a.pos ? a.pos : reinterpret_cast<const float*>(a.W), a.pos ? a.frames_per_clip * a.N * 4 : 0);
-        f32x4 pq[2][2][2];
-        v4i oq[2][2];
-        uint32_t offq[2][2], gq[2][2];
-        auto request = [&](int i, int b) {
-#pragma unroll
-          for (int rr = 0; rr < 2; ++rr) {
-            const int rloc = i * 16 + rr * 8;
-            const uint32_t m = (uint32_t)min(mrow0 + rloc, a.M - 1);
-            const uint32_t frame = a.div_tokens.div(m);  // rows per frame = tokens - 1 (the export has no CLS row)
-            const uint32_t t = frame - a.div_frames.div(frame) * (uint32_t)a.frames_per_clip;
-            offq[b][rr] = rloc < rows_left ? cbase + (uint32_t)rloc * (uint32_t)(a.ldc * 2) : 0xffffffffu;
-            gq[b][rr] = m * (uint32_t)(a.N >> 3) + (uint32_t)((nb + dc * 8) >> 3);  // dropout group (the launcher checks M * N / 8 < 2^32)
-            const uint32_t poff = a.pos ? (t * (uint32_t)a.N + (uint32_t)(nb + dc * 8)) * 4 : 0xffffffffu;  // no embedding: out of range reads 0
-            asm volatile(
-                "s_nop 4\n\t"
-                "buffer_load_dwordx4 %0, %3, %5, 0 offen\n\t"
-                "buffer_load_dwordx4 %1, %3, %5, 0 offen offset:16\n\t"
-                "buffer_load_dwordx4 %2, %4, %6, 0 offen"
-                : "=&v"(pq[b][rr][0]), "=&v"(pq[b][rr][1]), "=&v"(oq[b][rr])
-                : "v"(poff), "v"(offq[b][rr]), "s"(srdQw), "s"(srdRw)
-                : "memory");
-          }
-        };
-        request(0, 0);
-#pragma unroll
-        for (int i = 0; i < RB; ++i) {
-          __builtin_amdgcn_sched_barrier(0);
-          const int b = i & 1;
-          if (i + 1 < RB) request(i + 1, b ^ 1);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(parkf + (((j * 4 + eq) ^ er) << 4)) = acc[i][j];
-          if (i == 0) wait_vm<6>();
-          else if (i + 1 < RB) wait_vm<8>();
-          else wait_vm<2>();
-          asm volatile("" : "+v"(pq[b][0][0]), "+v"(pq[b][0][1]), "+v"(oq[b][0]), "+v"(pq[b][1][0]), "+v"(pq[b][1][1]), "+v"(oq[b][1]));
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int rr = 0; rr < 2; ++rr) {
-            const int row = rr * 8 + drow;
-            const f32x4 x0 = *reinterpret_cast<const f32x4*>(ep + row * 256 + (((2 * dc) ^ row) << 4));
-            const f32x4 x1 = *reinterpret_cast<const f32x4*>(ep + row * 256 + (((2 * dc + 1) ^ row) << 4));
-            float dv[8];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              dv[e] = x0[e];
-              dv[4 + e] = x1[e];
-            }
-            // the adapter's last nn.Dropout, before the residual add: element index row * N + column (a multiple of 8)
-            dfd_drop_eight(a.drop, (uint64_t)gq[b][rr] << 3, dv);
-            const bf16x8 ob = __builtin_bit_cast(bf16x8, oq[b][rr]);
-            bf16x8 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              o[e] = (bf16_t)((float)ob[e] + dv[e] + pq[b][rr][0][e]);
-              o[4 + e] = (bf16_t)((float)ob[4 + e] + dv[4 + e] + pq[b][rr][1][e]);
-            }
-            store_out(__builtin_bit_cast(v4i, o), srdC, offq[b][rr], a.stream_out);
-          }
-        }
-      } else if constexpr (CF8) {
-        // C as e4m3 of value * out_inv_scale: 4 passes of 32 rows x 64 B parked (2 KB); 8 wave-stores of 16 rows x 64 B
-        stores = RB;
-        const int srow = le >> 2, sc = le & 3;  // drain: row srow of a 16-row group, 16-byte chunk sc
-        unsigned char* const park8 = ep + er * 64 + eq * 4;  // + ii*1024, chunk j at position j ^ ((row >> 1) & 3)
-        const int psw = (er >> 1) & 3;
-        const unsigned char* const dsrc8 = ep + srow * 64 + ((sc ^ ((srow >> 1) & 3)) << 4);  // + rr*1024
-        const int64_t m8 = (int64_t)cur.m0 + wr * WROWS + srow;
-        const int rows_left8 = (int)min((int64_t)0x7fffffff, a.M - m8);
-        const uint32_t cbase8 = (uint32_t)(m8 * a.ldc + nb + sc * 16);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-#pragma unroll
-          for (int ii = 0; ii < 2; ++ii) {
-            const int i = 2 * q + ii;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              f32x4 v = activate(acc[i][j]) * a.out_inv_scale;
-#pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] = __builtin_fminf(__builtin_fmaxf(v[e], -448.0f), 448.0f);  // e4m3 saturates at +-448
-              unsigned pk = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0u, false);
-              pk = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], pk, true);
-              *reinterpret_cast<unsigned*>(park8 + ii * 1024 + ((j ^ psw) << 4)) = pk;
-            }
-          }
-#pragma unroll
-          for (int rr = 0; rr < 2; ++rr) {
-            const v4i d = *reinterpret_cast<const v4i*>(dsrc8 + rr * 1024);
-            const int rloc = q * 32 + rr * 16;
-            const uint32_t off = rloc < rows_left8 ? cbase8 + (uint32_t)rloc * (uint32_t)a.ldc : 0xffffffffu;
-            store_out(d, srdC, off, a.stream_out);
-          }
-        }
-      } else {
-      // C itself: 4 passes of 32 rows parked as bf16 (4 KB); 16 wave-stores of 8 rows x 128 B
-      unsigned char* const park = ep + er * 128 + ((eq ^ ((er & 7) << 1)) << 3);  // + ii*2048, ^ (j << 5)
-      const unsigned char* const dsrc = ep + drow * 128 + ((dc ^ drow) << 4);     // + rr*1024
-      const uint32_t cbase = (uint32_t)((mrow0 * a.ldc + nb + dc * 8) * 2);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-#pragma unroll
-        for (int ii = 0; ii < 2; ++ii) {
-          const int i = 2 * q + ii;
-          if (i >= RB) continue;  // 224-row tiles: the last pass holds 16 rows
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const f32x4 v = activate(acc[i][j]);
-            bf16x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = (bf16_t)v[e];
-            // row ii*16 + er, 8-byte unit (j*4 + eq) ^ ((row & 7) << 1)
-            // (the XOR is done on the LDS byte address and cast back to an LDS pointer: through a generic pointer the
-            // compiler loses the address space and emits flat_store, which also counts in vmcnt)
-            typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-            *reinterpret_cast<lds_bf16x4*>(((uint32_t)(uintptr_t)(lds_ptr_t)(park + ii * 2048)) ^ (uint32_t)(j << 5)) = o;
-          }
-        }
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-          if (q * 32 + rr * 8 >= WROWS) continue;
-          const v4i d = *reinterpret_cast<const v4i*>(dsrc + rr * 1024);
-          const int rloc = q * 32 + rr * 8;  // row of the store relative to this lane's first row
-          uint32_t off = rloc < rows_left ? cbase + (uint32_t)rloc * (uint32_t)(a.ldc * 2) : 0xffffffffu;  // out of range: dropped
-          store_out(d, srdC, off, a.stream_out);
-        }
-      }
-      }
+    for (int j = 0; j < 4; ++j) {
+      b4[j] = *reinterpret_cast<const f32x4*>(ep + (j * 16 + (le >> 4) * 4) * 4);
+      if constexpr (F8) cs4[j] = *reinterpret_cast<const f32x4*>(ep + 256 + (j * 16 + (le >> 4) * 4) * 4);
     }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // before the staging below overwrites them
+    const int stores = tile_epilogue<EPI, RB, F8, CF8>(a, acc, b4, cs4, ep, cur, wr, wc, le, D, srdC);
     if (!has_next) break;
-    // a wave's stores are all real only if all of its rows are inside M (see the header); else count none
-    s_prev = (int64_t)cur.m0 + wr * WROWS + WROWS <= a.M ? stores : 0;
+    s_prev = countable_stores<RB>(stores, cur, wr, a.M);
     idx = nidx;
     cur = nxt;
   }
@@ -705,137 +455,31 @@ bool sched_prepare(GemmArgs& a, hipStream_t st, int grid, int64_t ntiles) {
   return true;
 }
 
-template <int EPI, bool F8, bool CF8>
-int launch256e(const GemmArgs& a_in, hipStream_t st) {
-  GemmArgs a = a_in;
-  const int tiles_n = a.N / TN;
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) {
-      dfd_set_error("dfd_gemm(ping-pong): cannot query the device");
-      return DFD_ERR_LAUNCH;
-    }
-    n_cu = prop.multiProcessorCount;
+struct Gemm256e {
+  static constexpr const char* name = "ping-pong";
+  static constexpr bool spare_if_free = true;
+  static constexpr bool serves(int epi, bool f8) {
+    return epi == DFD_EPI_BIAS || epi == DFD_EPI_BIAS_QUICKGELU || epi == DFD_EPI_BIAS_GELU || epi == DFD_EPI_QKV_EXPORT || (!f8 && epi == DFD_EPI_RESIDUAL_POS);
   }
-  int cus = n_cu - a.spare_cus;
-  cus = cus < n_cu / 2 ? n_cu / 2 : cus;
-  if (a.spare_cus > 0 && a.spare_if_free) {
-    // a request, not an order: honoured where the rounds of tiles (at the better of the two tile heights) stay the same
-    auto cost = [&](int c) {
-      auto r = [&](int rows) { return (double)((((a.M + rows - 1) / rows) * tiles_n + c - 1) / c); };
-      const double r256 = r(256), r224 = r(224) * 0.97;
-      return (F8 || EPI == DFD_EPI_RESIDUAL_POS) ? (EPI == DFD_EPI_RESIDUAL_POS ? r224 : r256) : (r224 < r256 ? r224 : r256);
-    };
-    if (cost(cus) > cost(n_cu)) cus = n_cu;
+  // the loop is unrolled in pairs of K tiles around a head of two and a tail of four (RESIDUAL_POS: also the short form, 4)
+  static bool depth_ok(const GemmArgs& a, int esz, int nk, int epi) {
+    if ((nk < 6 && !(epi == DFD_EPI_RESIDUAL_POS && nk == 4)) || (nk & 1)) return false;
+    return (a.ldw * esz) % 128 == 0;  // the second piece of a W unit is addressed as (first ^ 64) + 8 rows
   }
-  // tile height: the one with the least (rounds of tiles) x (cost of a tile).  A 224-row tile saves the MFMA and
-  // epilogue work of 32 rows but stages as many bytes as a 256-row one, and the loop is bound by that staging:
-  // measured on the four ViT-B/16 shapes it costs 0.97 of a full tile, so it wins only where it saves a whole
-  // round (M = 94,560: N = 768 needs 5 rounds either way -> 224; N = 2304 / 3072: 15 vs 14, 20 vs 18 -> 256)
-  auto rounds = [&](int rows) {
-    const int64_t tiles = ((a.M + rows - 1) / rows) * tiles_n;
-    return (double)((tiles + cus - 1) / cus);
-  };
-  // (RESIDUAL_POS: 224-row tiles only — with 128 accumulator registers its read-modify-write epilogue, which also draws
-  // the dropout mask, does not fit the register file without spilling, and a spill would break the counted waits)
-  const bool use224 = !F8 && (EPI == DFD_EPI_RESIDUAL_POS || a.tile_rows == 224 || (a.tile_rows == 0 && rounds(224) * 0.97 < rounds(256)));
-  const int rows = use224 ? 224 : 256;
-  const int tiles_m = (int)((a.M + rows - 1) / rows);
-  const int64_t ntiles = (int64_t)tiles_m * tiles_n;
-  const int grid = (int)(ntiles < cus ? ntiles : cus);
-  const int nk = a.K / (F8 ? 128 : TK);
-  if (!F8 && nk >= 6 && a.no_dynamic == 0) sched_prepare(a, st, grid, ntiles);
-  else a.sched = nullptr;
-  if constexpr (F8) {
-    hipLaunchKernelGGL((gemm256e_kernel<EPI, 8, true, CF8>), dim3(grid), dim3(512), 0, st, a, tiles_m, tiles_n);
-  } else {
-    if (use224) hipLaunchKernelGGL((gemm256e_kernel<EPI, 7, false, false>), dim3(grid), dim3(512), 0, st, a, tiles_m, tiles_n);
-    else if constexpr (EPI != DFD_EPI_RESIDUAL_POS) hipLaunchKernelGGL((gemm256e_kernel<EPI, 8, false, false>), dim3(grid), dim3(512), 0, st, a, tiles_m, tiles_n);
+  static void prepare(GemmArgs& a, hipStream_t st, const TilePlan& p, bool f8) {
+    if (!f8 && a.K / TK >= 6 && a.no_dynamic == 0) sched_prepare(a, st, p.grid, p.ntiles);
+    else a.sched = nullptr;
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    dfd_set_error("dfd_gemm(ping-pong): launch failed: %s", hipGetErrorString(e));
-    return DFD_ERR_LAUNCH;
+  template <int EPI, int RB, bool F8, bool CF8>
+  static void run(int grid, hipStream_t st, const GemmArgs& a, int tiles_m, int tiles_n) {
+    hipLaunchKernelGGL((gemm256e_kernel<EPI, RB, F8, CF8>), dim3(grid), dim3(512), 0, st, a, tiles_m, tiles_n);
   }
-  return DFD_OK;
-}
-
-// shared eligibility: 0 = fine, 1 = not served
-int check256e(const GemmArgs& a, int esz, int csz, int kstep, bool short_k_ok = false) {
-  const int nk = a.K / kstep;  // the loop is unrolled in pairs of K tiles around a head of two and a tail of four
-  if (a.N % TN != 0 || a.K % kstep != 0 || (nk < 6 && !(short_k_ok && nk == 4)) || (nk & 1) || a.M < 1024) return 1;
-  if ((a.ldw * esz) % 128 != 0) return 1;  // the second piece of a W unit is addressed as (first ^ 64) + 8 rows
-  if ((a.lda * esz) % 16 != 0 || (a.ldw * esz) % 16 != 0 || (a.ldc * csz) % 16 != 0) return 1;
-  if ((reinterpret_cast<uintptr_t>(a.A) & 15) != 0 || (reinterpret_cast<uintptr_t>(a.W) & 15) != 0 || (reinterpret_cast<uintptr_t>(a.C) & 15) != 0) return 1;
-  if (a.bias && (reinterpret_cast<uintptr_t>(a.bias) & 15) != 0) return 1;
-  const int64_t lim = (int64_t)0xfffffff0;  // buffer descriptors carry 32-bit byte offsets
-  if (a.M * a.lda * esz > lim || (int64_t)a.N * a.ldw * esz > lim || a.M * a.ldc * csz > lim) return 1;
-  if ((int64_t)((a.M + 223) / 224) * (a.N / TN) > 0x3fffffff || a.M >= ((int64_t)1 << 31)) return 1;
-  return 0;
-}
-
-int check_export_e(const GemmArgs& a) {
-  if ((a.N / (3 - a.qkv_first)) % TN != 0) return 1;
-  if (a.pos && (reinterpret_cast<uintptr_t>(a.pos) & 15) != 0) return 1;
-  if (a.k_export && (a.M / a.tokens) * (a.tokens - 1) * (int64_t)(a.N / (3 - a.qkv_first)) * 2 > (int64_t)0xfffffff0) return 1;
-  return 0;
-}
+};
 
 }  // namespace
 
 // 0 = launched, <0 = error, 1 = shape / epilogue not served by this kernel
-int dfd_gemm256e_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st) {
-  if (c_dtype != DFD_BF16 || check256e(a, 2, 2, 64, epi == DFD_EPI_RESIDUAL_POS)) return 1;
-  switch (epi) {
-    case DFD_EPI_BIAS:
-      return launch256e<DFD_EPI_BIAS, false, false>(a, st);
-    case DFD_EPI_BIAS_QUICKGELU:
-      return launch256e<DFD_EPI_BIAS_QUICKGELU, false, false>(a, st);
-    case DFD_EPI_BIAS_GELU:
-      return launch256e<DFD_EPI_BIAS_GELU, false, false>(a, st);
-    case DFD_EPI_QKV_EXPORT: {
-      if (check_export_e(a)) return 1;
-      GemmArgs b = a;
-      b.div_tokens = FastDiv::make((uint32_t)a.tokens);
-      b.div_frames = FastDiv::make((uint32_t)a.frames_per_clip);
-      return launch256e<DFD_EPI_QKV_EXPORT, false, false>(b, st);
-    }
-    case DFD_EPI_RESIDUAL_POS: {
-      if (check256e(a, 2, 2, 64, true) || a.tokens < 2 || a.M * (int64_t)(a.N >> 3) >= ((int64_t)1 << 32)) return 1;
-      if (a.pos && ((reinterpret_cast<uintptr_t>(a.pos) & 15) != 0 || a.frames_per_clip < 1)) return 1;
-      if (a.residual && (reinterpret_cast<uintptr_t>(a.residual) & 15) != 0) return 1;
-      GemmArgs b = a;
-      b.div_tokens = FastDiv::make((uint32_t)(a.tokens - 1));  // rows per frame
-      b.div_frames = FastDiv::make((uint32_t)(a.frames_per_clip > 0 ? a.frames_per_clip : 1));
-      return launch256e<DFD_EPI_RESIDUAL_POS, false, false>(b, st);
-    }
-    default:
-      return 1;
-  }
-}
+int dfd_gemm256e_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st) { return try_persistent<Gemm256e, false>(a, c_dtype, epi, st); }
 
 // fp8 (e4m3) operands on the block-scaled matrix cores; C bf16, or e4m3 for the plain / QuickGELU / GELU epilogues
-int dfd_gemm256e_f8_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st) {
-  if (c_dtype != DFD_BF16 && c_dtype != DFD_FP8) return 1;
-  if (!a.col_scale || (reinterpret_cast<uintptr_t>(a.col_scale) & 15) != 0) return 1;
-  if (check256e(a, 1, c_dtype == DFD_FP8 ? 1 : 2, 128)) return 1;
-  switch (epi) {
-    case DFD_EPI_BIAS:
-      return c_dtype == DFD_FP8 ? launch256e<DFD_EPI_BIAS, true, true>(a, st) : launch256e<DFD_EPI_BIAS, true, false>(a, st);
-    case DFD_EPI_BIAS_QUICKGELU:
-      return c_dtype == DFD_FP8 ? launch256e<DFD_EPI_BIAS_QUICKGELU, true, true>(a, st) : launch256e<DFD_EPI_BIAS_QUICKGELU, true, false>(a, st);
-    case DFD_EPI_BIAS_GELU:
-      return c_dtype == DFD_FP8 ? launch256e<DFD_EPI_BIAS_GELU, true, true>(a, st) : launch256e<DFD_EPI_BIAS_GELU, true, false>(a, st);
-    case DFD_EPI_QKV_EXPORT: {
-      if (c_dtype != DFD_BF16 || check_export_e(a)) return 1;
-      GemmArgs b = a;
-      b.div_tokens = FastDiv::make((uint32_t)a.tokens);
-      b.div_frames = FastDiv::make((uint32_t)a.frames_per_clip);
-      return launch256e<DFD_EPI_QKV_EXPORT, true, false>(b, st);
-    }
-    default:
-      return 1;
-  }
-}
+int dfd_gemm256e_f8_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st) { return try_persistent<Gemm256e, true>(a, c_dtype, epi, st); }

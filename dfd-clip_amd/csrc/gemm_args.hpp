@@ -1,4 +1,6 @@
-// Argument block shared by the GEMM kernels (gemm.hip: general shapes; gemm256.hip: tuned bf16).
+// Argument block shared by the GEMM kernels: gemm.hip (general shapes, 128-wide tiles), gemm256.hip (tuned bf16, one
+// workgroup per tile) and the two persistent kernels gemm256e.hip / gemm256p.hip (bf16 and e4m3 operands; their shared
+// epilogue, tile plan and dispatch are in gemm256p_common.hpp).
 #pragma once
 #include "dropout.hpp"
 
@@ -20,7 +22,7 @@ struct GemmArgs {
   int spare_if_free;  // DFD_GEMM_SPARE_IF_FREE: ... only where that costs no extra round of tiles
   int tile_rows;  // persistent kernel: 0 = choose, 224 / 256 = force that tile height (lab, tests)
   DfdDrop drop;   // RESIDUAL_POS: dropout on the accumulator (element index row*N + col); thr16 == 0: none
-  FastDiv div_tokens, div_frames;  // persistent kernel, QKV_EXPORT: row -> (frame, token), frame -> frame % T
+  FastDiv div_tokens, div_frames;  // persistent kernels, QKV_EXPORT / RESIDUAL_POS: row -> (frame, token), frame -> frame % T
   const float* col_scale;          // fp8 operands: per output column, activation scale x weight-row scale
   float out_inv_scale;             // fp8 output: stored value = e4m3(result * out_inv_scale)
   // gemm256e.hip, dynamic tile hand-out (set by its launcher): eight monotonic counters, one 128-byte line per XCD label
@@ -30,9 +32,9 @@ struct GemmArgs {
   int no_dynamic;  // tests / A-B: 1 = keep the static order
 };
 
-// tuned bf16 kernels: 0 = launched, <0 = error, 1 = shape / epilogue not eligible
-int dfd_gemm256_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st);   // gemm256.hip: one workgroup per tile
-int dfd_gemm256p_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st);  // gemm256p.hip: persistent, bf16 C
-int dfd_gemm256p_f8_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st);  // same kernel, e4m3 operands (dfd_gemm_fp8)
+// tuned kernels: 0 = launched, <0 = error, 1 = shape / epilogue not eligible
+int dfd_gemm256_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st);      // gemm256.hip: one workgroup per tile
 int dfd_gemm256e_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st);     // gemm256e.hip: persistent, ping-pong K loop (tried first)
-int dfd_gemm256e_f8_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st);  // same kernel, e4m3 operands
+int dfd_gemm256e_f8_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st);  // same kernel, e4m3 operands (dfd_gemm_fp8)
+int dfd_gemm256p_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st);     // gemm256p.hip: persistent, the K depths gemm256e does not serve
+int dfd_gemm256p_f8_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st);  // same kernel, e4m3 operands

@@ -454,6 +454,56 @@ def test_pingpong_residual_pos_equals_relaunching(capi, M, N, K, in_place, p):
         assert torch.equal(got, want)
 
 
+@pytest.mark.parametrize("K", [384, 320])
+def test_persistent_gemm_raw_export_without_pos(capi, K):
+    """QKV_EXPORT with k_export / v_export and pos=None (the raw export an adapter reads) on both persistent kernels, which
+    share one epilogue: it adds zeros and issues no embedding load.  K = 384 is the ping-pong kernel's shortest depth
+    (variant 1 hands it to gemm256p), K = 320 (5 steps) is served by gemm256p only.  M = 1120 rows = 160 frames of 7
+    tokens: five row panels, full at 224 rows, the last one ragged at 256.  Against fp64 on the same bf16 operands (f32
+    accumulation order + one rounding: rtol 2^-8), CLS rows dropped, every export row written; the two kernels agree bit
+    for bit, and so does the K | V-only call."""
+    tokens, N = 7, 768
+    D = N // 3
+    M = 1120 // tokens * tokens
+    g = torch.Generator(device="cuda").manual_seed(K)
+    a = torch.randn(M, K, device="cuda", generator=g).to(torch.bfloat16)
+    w = (torch.randn(N, K, device="cuda", generator=g) * K ** -0.5).to(torch.bfloat16)
+    bias = torch.randn(N, device="cuda", generator=g) * 0.1
+    ref = a.double() @ w.double().T + bias.double()
+    fv = ref.view(M // tokens, tokens, 3, D)
+
+    def run(path, **opts):
+        c = torch.full((M, N), float("nan"), device="cuda", dtype=torch.bfloat16)
+        ke = torch.full((M // tokens * (tokens - 1), D), float("nan"), device="cuda", dtype=torch.bfloat16)
+        ve = torch.full_like(ke, float("nan"))
+        capi.gemm(a, w, c, bias, capi.EPI_QKV_EXPORT, pos=None, k_export=ke, v_export=ve, tokens=tokens, **opts)
+        assert capi.gemm_last_path() == path
+        assert_close(c, ref, 1e-4, 2 ** -8, f"qkv {opts}")  # (also: no NaN of the pre-fill left)
+        assert_close(ke.view(-1, tokens - 1, D), fv[:, 1:, 1], 1e-4, 2 ** -8, f"k export {opts}")
+        assert_close(ve.view(-1, tokens - 1, D), fv[:, 1:, 2], 1e-4, 2 ** -8, f"v export {opts}")
+        # K and V blocks alone (qkv_first=1): identical exports and columns, the query block untouched
+        c2, ke2, ve2 = torch.full_like(c, float("nan")), torch.full_like(ke, float("nan")), torch.full_like(ve, float("nan"))
+        capi.gemm(a, w[D:], c2[:, D:], bias[D:], capi.EPI_QKV_EXPORT, pos=None, k_export=ke2, v_export=ve2, tokens=tokens, qkv_first=1, **opts)
+        assert capi.gemm_last_path() == path
+        assert torch.equal(ke2, ke) and torch.equal(ve2, ve) and torch.equal(c2[:, D:], c[:, D:]), opts
+        assert torch.isnan(c2[:, :D].float()).all(), "the query block must not be written"
+        return c, ke, ve
+
+    first = 257 if K == 384 else 256
+    base = run(first)  # 224-row tiles (the launcher's choice here)
+    ragged = run(first, tile_blocks=8)
+    for x, y in zip(base, ragged):
+        assert torch.equal(x, y), "256-row tiles"
+    if K == 384:
+        capi.gemm_set_variant(1)
+        try:
+            for opts in (dict(), dict(tile_blocks=8)):
+                for x, y in zip(base, run(256, **opts)):
+                    assert torch.equal(x, y), ("variant 1", opts)
+        finally:
+            capi.gemm_set_variant(0)
+
+
 @pytest.mark.parametrize("res,patch,width", [(224, 16, 768), (224, 14, 1024)])
 def test_patch_embed_tuned_kernel(capi, res, patch, width):
     """PATCH_EMBED epilogue of the tuned kernel (M = frames*P >= 1024): conv1 + CLS row + positional embedding at
