@@ -69,6 +69,7 @@ def build(force=False, verbose=False, extra_flags=()):
     headers = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".hpp")]
     headers.append(os.path.join(INCLUDE, "dfdclip.h"))
     headers.append(os.path.join(INCLUDE, "dfdclip_ext.h"))
+    headers.append(os.path.join(INCLUDE, "dfdclip_explain.h"))
     jobs, objs = [], []
     for src in sources():
         sp = os.path.join(CSRC, src)

@@ -147,6 +147,12 @@ EXT_SIGNATURES = {
                                        c_void_p, c_int64, c_int64, c_int, c_float, c_float, c_void_p]),
 }
 
+# explanation entry points beside the ABI, in a header of their own (include/dfdclip_explain.h)
+EXPLAIN_SIGNATURES = {
+    "dfd_decoder_attn_map": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                     c_int, c_int, c_int, c_void_p]),
+}
+
 # test / measurement hooks outside the ABI header (include/dfdclip_hooks.h)
 HOOK_SIGNATURES = {
     "dfd_attention_set_variant": (c_int, [c_int]),
@@ -166,7 +172,7 @@ def load_library(path=None):
     if not os.path.exists(path):
         raise DfdError(f"{path} not found: the HIP kernel library is not built and there is no fallback path")
     lib = ctypes.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **HOOK_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **EXPLAIN_SIGNATURES, **HOOK_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError:
@@ -546,6 +552,25 @@ def decoder_attn_modes_fwd(q, k, frame_mask, modes, scores, weights, B, T, patch
                                                      _ptr(weights), B, T, patches, heads, d, _stream()),
            "dfd_decoder_attn_modes_fwd")
     return weights
+
+
+def decoder_attn_map(q, k, frame_mask, stats, aff, B, T, patches, heads, d=64, ext_weights=None, branches=None, pos=None):
+    """aff [B,heads,S] f32 = the per-key weight ½(softmax + CoDA) that `decoder_attn_fwd` applied to v, from the `stats` it
+    wrote (or `ext_weights` under attn_mode; `stats` may then be None); `branches` [2,B,heads,S]: the two weights without
+    the ½.  K as for the forward: dense, or a strided view with `pos` added on the fly."""
+    _dev(q, k, frame_mask, stats, aff, ext_weights, branches)
+    assert q.dtype == torch.float32 and q.is_contiguous()
+    assert frame_mask.dtype == torch.uint8 and frame_mask.is_contiguous()
+    n = B * heads * T * patches
+    assert aff.dtype == torch.float32 and aff.is_contiguous() and aff.numel() == n
+    assert stats is None or (stats.dtype == torch.float32 and stats.is_contiguous() and stats.numel() == B * heads * 2)
+    assert ext_weights is None or (ext_weights.dtype == torch.float32 and ext_weights.is_contiguous() and ext_weights.numel() == n)
+    assert branches is None or (branches.dtype == torch.float32 and branches.is_contiguous() and branches.numel() == 2 * n)
+    lay, _keep = _kv_layout(k, None, pos, B, T, patches, heads * d)
+    _check(load_library().dfd_decoder_attn_map(_ptr(q), _ptr(k), _DTYPE[k.dtype], lay, _ptr(frame_mask), _ptr(stats), _ptr(ext_weights),
+                                               _ptr(aff), _ptr(branches), B, T, patches, heads, d, _stream()),
+           "dfd_decoder_attn_map")
+    return aff
 
 
 def decoder_attn_modes_bwd(scores, v, dmix, modes, dwv_ws, dscores, B, T, patches, heads, d=64, pos=None):

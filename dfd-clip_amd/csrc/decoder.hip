@@ -97,12 +97,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 512 ? (POS ? 2 : 3) : 4)) void decod
       [[maybe_unused]] float pe[8];
       if constexpr (POS) Ld8<float>::load(pb + po[u], pe);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float kk = POS ? kr[u].get(e) + pe[e] : kr[u].get(e);
-        ds = fmaf(qs[e], kk, ds);
-        dc = fmaf(qc[e] * 0.125f, kk, dc);
-        l1 += fabsf(qc[e] - kk);
-      }
+      for (int e = 0; e < 8; ++e) key_channel(POS ? kr[u].get(e) + pe[e] : kr[u].get(e), qs[e], qc[e], ds, dc, l1);
       pds[u] = ds;
       pdc[u] = dc;
       pl1[u] = l1;
@@ -127,8 +122,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 512 ? (POS ? 2 : 3) : 4)) void decod
       p = ok ? __expf(ds - mx) : 0.f;
       l_own += p;
     }
-    const float gate = 2.0f / (1.0f + __expf(l1 * 0.125f));  // 2·sigmoid(−l1/√d)
-    const float c = ok ? fast_tanh(dc) * gate : 0.f;
+    const float c = ok ? coda_weight(dc, l1) : 0.f;  // tanh(dc) · 2·sigmoid(−l1/√d)
 #pragma unroll
     for (int u = 0; u < UN; ++u) {
       const float pu = __shfl(p, lane_base + u, 64), cu = __shfl(c, lane_base + u, 64);

@@ -1,5 +1,6 @@
-// Pieces shared by the decoder's forward (decoder.hip) and backward (decoder_bwd.hip) kernels: 8-element row pieces
-// (one lane's share of a 64-wide head), the exchanges inside an 8-lane head group, tanh.
+// Pieces shared by the decoder's forward (decoder.hip), backward (decoder_bwd.hip) and attention-map (decoder_map.hip)
+// kernels: 8-element row pieces (one lane's share of a 64-wide head), the exchanges inside an 8-lane head group, tanh, a
+// key row's three sums and its CoDA weight.
 #pragma once
 #include "common.hpp"
 
@@ -75,6 +76,21 @@ __device__ __forceinline__ float fast_tanh(float x) {
   // tanh(x) = 1 - 2/(exp(2x)+1); exact limits at +-inf, abs error ~1e-7 around 0
   const float e = __expf(2.0f * x);
   return 1.0f - 2.0f / (e + 1.0f);
+}
+
+// One channel of a key row folded into the lane's three partial sums against the clip's query: ds += q_s·k/√d (qs is
+// pre-scaled), dc += q_c·k/√d, l1 += |q_c − k|, d = 64.  Shared by the forward (decoder.hip) and the attention map
+// (decoder_map.hip), so that both form the same bits.
+__device__ __forceinline__ void key_channel(float kk, float qs, float qc, float& ds, float& dc, float& l1) {
+  ds = fmaf(qs, kk, ds);
+  dc = fmaf(qc * 0.125f, kk, dc);
+  l1 += fabsf(qc - kk);
+}
+
+// CoDA weight of a key from its reduced sums: tanh(q_c·k/√d) · 2·sigmoid(−‖q_c − k‖₁/√d), d = 64
+__device__ __forceinline__ float coda_weight(float dc, float l1) {
+  const float gate = 2.0f / (1.0f + __expf(l1 * 0.125f));
+  return fast_tanh(dc) * gate;
 }
 
 }  // namespace

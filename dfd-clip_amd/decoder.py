@@ -247,11 +247,17 @@ class Decoder(RuntimeStateMixin, nn.Module):
             return None
         return capi.Dropout(drop_rng, site, self.dropout_p)
 
-    def run(self, kvs, m, drop_rng=None):
+    def run(self, kvs, m, drop_rng=None, attention=None):
         """-> (raw logits list, video_feature, normalised logits list).  With grad enabled and any
         trainable parameter, goes through `_DecoderFn` so `loss.backward()` reaches the parameters.
-        `drop_rng`: this step's dropout state (device int64 {seed, step}) in train mode, None = no dropout."""
+        `drop_rng`: this step's dropout state (device int64 {seed, step}) in train mode, None = no dropout.
+        `attention`: a preallocated f32 [L, B, heads, T*P] tensor that receives, per block, the per-key weight
+        ½(softmax + CoDA) the block applied to its values (`capi.decoder_attn_map`); the no-grad path only."""
         k_all, v_all, kv_pos, mask, B, T, P = self._unpack(kvs, m)
+        if attention is not None:
+            want = (k_all.shape[0], B, self.heads, T * P)
+            if attention.dtype != torch.float32 or tuple(attention.shape) != want or not attention.is_contiguous():
+                raise ValueError(f"attention must be a contiguous f32 tensor of shape {want}")
         if self.dropout_p <= 0:
             drop_rng = None
         if self._param_list is None:  # the module tree is static: walk it once, not every step
@@ -259,15 +265,19 @@ class Decoder(RuntimeStateMixin, nn.Module):
         names = [n for n, p in self._param_list]
         params = [p for n, p in self._param_list]
         if torch.is_grad_enabled() and (any(p.requires_grad for p in params) or k_all.requires_grad):
+            if attention is not None:
+                raise NotImplementedError("attention maps come from the no-grad forward: call under torch.no_grad()")
             out = _DecoderFn.apply(self, k_all, v_all, mask, (B, T, P), names, (drop_rng, kv_pos), *params)
             n = len(self.out_dims)
             return list(out[1:1 + n]), out[0], list(out[1 + n:1 + 2 * n])
         w = {n: p.detach() for n, p in zip(names, params)}
-        raws, feat, outs, _ = self._forward_kernels(w, k_all, v_all, mask, B, T, P, save=False, drop_rng=drop_rng, kv_pos=kv_pos)
+        raws, feat, outs, _ = self._forward_kernels(w, k_all, v_all, mask, B, T, P, save=False, drop_rng=drop_rng, kv_pos=kv_pos,
+                                                    attention=attention)
         return raws, feat, outs
 
     # ---- forward on HIP kernels --------------------------------------------------------------
-    def _forward_kernels(self, w, k_all, v_all, mask, B, T, P, save, drop_rng=None, kv_pos=None):
+    def _forward_kernels(self, w, k_all, v_all, mask, B, T, P, save, drop_rng=None, kv_pos=None, attention=None):
+        assert attention is None or not save
         dev = k_all.device
         D, H, L = self.width, self.heads, k_all.shape[0]
         f32 = dict(device=dev, dtype=torch.float32)
@@ -321,6 +331,8 @@ class Decoder(RuntimeStateMixin, nn.Module):
                         mode_ws = (new(B, H, T * P), new(B, H, T * P))
                     aw = capi.decoder_attn_modes_fwd(q, k_all[i], mask, self.attn_modes, mode_ws[0], mode_ws[1], B, T, P, H, pos=kv_pos)
                 capi.decoder_attn_fwd(q, k_all[i], v_all[i], mask, mix, stats, ws, splits, B, T, P, H, ext_weights=aw, pos=kv_pos)
+                if attention is not None:  # the weights this call applied: same q, stats / aw and key layout
+                    capi.decoder_attn_map(q, k_all[i], mask, stats, attention[i], B, T, P, H, ext_weights=aw, pos=kv_pos)
                 lin(mix, pre + "attn.out_proj.", x, capi.EPI_BIAS_RESIDUAL)
                 capi.layernorm(x, g(pre + "ln_2.weight"), g(pre + "ln_2.bias"), h)
                 lin(h, pre + "mlp.c_fc.", u, capi.EPI_BIAS_QUICKGELU)

@@ -324,12 +324,28 @@ class Detector(RuntimeStateMixin, nn.Module):
                 # there (models.py:673 -> NameError); there is no behaviour to match
                 raise NotImplementedError(f"train_mode.{key}: this branch raises in the reference itself (models.py:604, :673)")
         if "patch_mask" in self.train_mode:
-            if self.train_mode.patch_mask.type not in ("batch", "sample"):
-                # "guide" reads a pickled saliency map (models.py:494-496): unpickling foreign files is not done here
+            if self.train_mode.patch_mask.type not in ("batch", "sample", "guide"):
                 raise NotImplementedError(f"patch_mask.type={self.train_mode.patch_mask.type} is not built")
             if self.adapter is not None and self.adapter.struct.endswith("nln"):
                 raise NotImplementedError("patch_mask with the nln adapter: its LayerNorm is sized for all patches "
                                           "(the reference fails on this combination too)")
+            self.guide_map = None
+            if self.train_mode.patch_mask.type == "guide":
+                # models.py:494-496 unpickles the map; here it is an .npz (harness.load_guide: no unpickling of foreign
+                # files).  p of np.random.choice must sum to 1 within its own tolerance: renormalised in float64.
+                from .harness import load_guide
+                path = self.train_mode.patch_mask.path if "path" in self.train_mode.patch_mask else None
+                if not path:
+                    raise ValueError("patch_mask.type=guide needs patch_mask.path: an .npz written by harness.save_guide")
+                grid = self.encoder.input_resolution // self.encoder.patch_size
+                v = np.asarray(load_guide(path)["v"], dtype=np.float64)
+                if v.ndim != 3 or v.shape[1:] != (grid, grid) or v.shape[0] <= max(self.layer_indices):
+                    raise ValueError(f"guide map {path}: 'v' is {v.shape}, this model needs [layers > {max(self.layer_indices)}, "
+                                     f"{grid}, {grid}]")
+                if not np.isfinite(v).all() or (v < 0).any() or (v.reshape(len(v), -1).sum(1)[self.layer_indices] <= 0).any():
+                    raise ValueError(f"guide map {path}: every tapped layer's map must be finite, non-negative and not all zero")
+                tot = v.reshape(len(v), -1).sum(1)
+                self.guide_map = {"v": v / np.where(tot > 0, tot, 1.0)[:, None, None]}
 
     @torch.no_grad()
     def calibrate_fp8(self, x, margin=1.0):
@@ -549,8 +565,11 @@ class Detector(RuntimeStateMixin, nn.Module):
         g.replay()
         return True
 
-    def predict(self, x, m, with_video_features=False, with_adapt_features=False, train=False):
-        """x [B,T,3,R,R], m [B,T] bool -> (task_logits list of [B,out_dim] with L2 norm 5, features)."""
+    def predict(self, x, m, with_video_features=False, with_adapt_features=False, train=False, with_attention=False):
+        """x [B,T,3,R,R], m [B,T] bool -> (task_logits list of [B,out_dim] with L2 norm 5, features).
+        `with_attention`: features["attention"] = per tapped layer the f32 [B, heads, T, patches] weight that the decoder
+        block applied to each key's value, ½(softmax + CoDA) (CoDA weights can be negative); padded frames are 0.  The
+        no-grad forward only; the logits are the bits of the same call without it."""
         b, t, c, h, w = x.shape
         if t != self.num_frames and self.decoder.positional_embedding is not None:
             raise RuntimeError(f"The size of tensor a ({t}) must match the size of tensor b ({self.num_frames}) "
@@ -575,7 +594,10 @@ class Detector(RuntimeStateMixin, nn.Module):
             num_select = int(P * self.train_mode.patch_mask.ratio)
             ks, vs, idx = [], [], None
             for i in range(len(self.layer_indices)):
-                if idx is None or self.train_mode.patch_mask.type == "sample":
+                if self.train_mode.patch_mask.type == "guide":  # the reference's call in its order (models.py:533-539)
+                    idx = torch.as_tensor(np.random.choice(range(P), num_select, replace=False,
+                                                           p=self.guide_map["v"][self.layer_indices[i]].flatten()), device=kr.device)
+                elif idx is None or self.train_mode.patch_mask.type == "sample":
                     idx = torch.as_tensor(np.random.choice(range(P), num_select, replace=False), device=kr.device)
                 ks.append(kr[i].view(b * t, P, -1).index_select(1, idx).reshape(b * t * num_select, -1))
                 vs.append(vr[i].view(b * t, P, -1).index_select(1, idx).reshape(b * t * num_select, -1))
@@ -603,10 +625,17 @@ class Detector(RuntimeStateMixin, nn.Module):
             kv = self.adapter.run(kv[0], kv[1], t, pos, drop_rng)
         if pipe is not None:
             self.decoder._after_backward = pipe[2].record  # recorded on the backward's stream when it ends
-        _, video_features, task_logits = self.decoder.run(kv, m, drop_rng)
+        attention = None
+        if with_attention:
+            k0 = kv[0]
+            p_ = k0.shape[2] if k0.dim() == 4 else k0.shape[1] // (b * t)
+            attention = torch.empty(k0.shape[0], b, self.encoder.heads, t * p_, device=k0.device, dtype=torch.float32)
+        _, video_features, task_logits = self.decoder.run(kv, m, drop_rng, attention=attention)
         if pipe is not None:
             pipe[1].record(pipe[0])
         features = {}
+        if with_attention:
+            features["attention"] = [attention[i].view(b, self.encoder.heads, t, -1) for i in range(attention.shape[0])]
         if with_video_features:
             features["video"] = video_features
         if with_adapt_features:
@@ -619,6 +648,22 @@ class Detector(RuntimeStateMixin, nn.Module):
             else:
                 raise Exception("cannot return adaptive features without an adapter")
         return task_logits, features
+
+    @torch.no_grad()
+    def saliency(self, x, m, reduce="mean"):
+        """-> f32 [B, L, T, g, g] (L tapped layers, g = sqrt(patches)): the decoder's per-key weight of
+        `predict(with_attention=True)` with the heads reduced by `reduce` ("mean" or "max").  The weight is
+        ½(softmax + CoDA) taken as is: the CoDA branch is tanh·gate, so entries can be NEGATIVE (a key that pushes the mix
+        away from its value); nothing is clamped or renormalised.  Padded frames are 0."""
+        if reduce not in ("mean", "max"):
+            raise ValueError(f"reduce={reduce!r}: 'mean' or 'max'")
+        _, features = self.predict(x, m, with_attention=True)
+        a = torch.stack(features["attention"], dim=1)  # [B, L, heads, T, P]
+        a = a.mean(dim=2) if reduce == "mean" else a.amax(dim=2)
+        g = int(round(a.shape[-1] ** 0.5))
+        if g * g != a.shape[-1]:
+            raise ValueError(f"{a.shape[-1]} patches are not a square grid")
+        return a.view(*a.shape[:3], g, g)
 
     def _build_adapter(self, config, num_frames):
         """`adapter.type` none / normal (fresh) / pretrain (parameters from a checkpoint of a whole Detector, optionally

@@ -230,3 +230,66 @@ def infer_videos(model, videos, batch_size=30, modality="video", task_index=0, d
     pred2 = torch.cat([probs.argmax(dim=-1), torch.tensor([0, 1])])
     return dict(accuracy=round((pred2 == lab2).float().mean().item(), 3), roc_auc=round(binary_auroc(lab2, sc2), 3),
                 labels=labels, probs=probs)
+
+
+# ---- patch saliency guides (train_mode.patch_mask.type: guide) -----------------------------------------------------
+
+@torch.no_grad()
+def saliency_guide(model, batches):
+    """The map `patch_mask.type: guide` samples from (reference models.py:533-539: `guide_map['v'][layer]`), measured on
+    this model: |aff| of `predict(with_attention=True)` averaged over clips, unpadded frames and heads, per tapped layer,
+    accumulated on the device.  `batches`: an iterable of (frames [B,T,3,R,R], mask [B,T]).
+    -> {"v": float64 ndarray [tower layers, g, g]}; each tapped layer's map sums to 1, untapped layers are uniform."""
+    import numpy as np
+    m = getattr(model, "module", model)
+    acc, frames = None, 0
+    for x, mask in batches:
+        _, features = m.predict(x, mask, with_attention=True)
+        a = torch.stack(features["attention"]).abs().to(torch.float64)  # [L, B, heads, T, P]; padded frames are 0
+        part = a.sum(dim=(1, 3)).mean(dim=1)                             # [L, P]
+        acc = part if acc is None else acc + part
+        frames += int(mask.sum())
+    if acc is None or frames == 0:
+        raise ValueError("saliency_guide: no unpadded frame in `batches`")
+    acc = (acc / frames).cpu().numpy()
+    patches = acc.shape[1]
+    g = int(round(patches ** 0.5))
+    if g * g != patches:
+        raise ValueError(f"{patches} patches are not a square grid")
+    layers = len(m.encoder.transformer.resblocks) if hasattr(m.encoder, "transformer") else max(m.layer_indices) + 1
+    v = np.full((layers, g, g), 1.0 / patches, dtype=np.float64)
+    for i, l in enumerate(m.layer_indices):
+        tot = acc[i].sum()
+        if not np.isfinite(tot) or tot <= 0:
+            raise ValueError(f"saliency_guide: layer {l} has no finite attention mass")
+        v[l] = (acc[i] / tot).reshape(g, g)
+    return {"v": v}
+
+
+_GUIDE_HINT = ("guide maps are read and written as .npz only (no unpickling of foreign files); convert the reference's pickle "
+               "once, where you trust it: np.savez(path, v=np.stack([guide_map['v'][l] for l in range(layers)]))")
+
+
+def save_guide(path, guide):
+    """Writes {"v": [layers, g, g]} as an .npz (float64)."""
+    import numpy as np
+    if not str(path).endswith(".npz"):
+        raise ValueError(f"{path}: {_GUIDE_HINT}")
+    v = np.asarray(guide["v"], dtype=np.float64)
+    if v.ndim != 3 or v.shape[1] != v.shape[2]:
+        raise ValueError(f"guide 'v' must be [layers, g, g], got {v.shape}")
+    np.savez(path, v=v)
+
+
+def load_guide(path):
+    """-> {"v": float64 ndarray [layers, g, g]} from an .npz written by `save_guide` (allow_pickle=False)."""
+    import numpy as np
+    if not str(path).endswith(".npz"):
+        raise ValueError(f"{path}: {_GUIDE_HINT}")
+    with np.load(path, allow_pickle=False) as z:
+        if "v" not in z.files:
+            raise ValueError(f"{path}: no array 'v' ({_GUIDE_HINT})")
+        v = np.asarray(z["v"], dtype=np.float64)
+    if v.ndim != 3 or v.shape[1] != v.shape[2]:
+        raise ValueError(f"{path}: 'v' must be [layers, g, g], got {v.shape}")
+    return {"v": v}
