@@ -507,6 +507,12 @@ extern "C" int dfd_decoder_attn_fwd(const float* q, const void* k, const void* v
   DFD_REQUIRE(d == HD, "dfd_decoder_attn_fwd: head dim %d, only 64 is supported", d);
   DFD_REQUIRE(B >= 0 && T > 0 && patches > 0 && heads > 0 && heads * HD <= 1024, "dfd_decoder_attn_fwd: bad shape");
   DFD_REQUIRE(splits > 0 && splits <= 4096, "dfd_decoder_attn_fwd: splits=%d", splits);
+  // decoder_attn_combine_kernel keeps one rescale weight per (head, split) in LDS beside its two static rows; what no
+  // launch can get is refused here, before the partial kernel is launched, rather than by the combine launch
+  const size_t combine_lds = (size_t)heads * splits * sizeof(float), combine_static = 2 * 16 * sizeof(float);
+  DFD_REQUIRE(combine_lds + combine_static <= 160 * 1024,
+              "dfd_decoder_attn_fwd: splits=%d with heads=%d needs %zu B of LDS to merge (heads*splits <= 40928)", splits, heads,
+              combine_lds);
   DFD_REQUIRE(kv_dtype == DFD_F32 || kv_dtype == DFD_BF16, "dfd_decoder_attn_fwd: kv_dtype=%d", kv_dtype);
   DFD_REQUIRE(dfd_aligned16(k) && dfd_aligned16(v) && dfd_aligned16(q), "dfd_decoder_attn_fwd: pointers must be 16-byte aligned");
   if (int rc = check_kv_layout("dfd_decoder_attn_fwd", layout, kv_dtype, heads * HD)) return rc;
@@ -540,7 +546,10 @@ extern "C" int dfd_decoder_attn_fwd(const float* q, const void* k, const void* v
 #undef PARTIAL_LAUNCH
 #undef PARTIAL_LAUNCH1
   DFD_CHECK_LAUNCH("dfd_decoder_attn_fwd(partial)");
-  hipLaunchKernelGGL(decoder_attn_combine_kernel, dim3(B), dim3(heads * HD), (size_t)heads * splits * sizeof(float), st, ws, mix,
+  if (combine_lds + combine_static > 64 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&decoder_attn_combine_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)combine_lds);
+  hipLaunchKernelGGL(decoder_attn_combine_kernel, dim3(B), dim3(heads * HD), combine_lds, st, ws, mix,
                      mix_softmax, stats, splits, heads);
   DFD_CHECK_LAUNCH("dfd_decoder_attn_fwd(combine)");
   return DFD_OK;
@@ -577,7 +586,9 @@ extern "C" int dfd_decoder_attn_modes_fwd(const float* q, const void* k, int kv_
   DFD_REQUIRE(kv_dtype == DFD_F32 || kv_dtype == DFD_BF16, "dfd_decoder_attn_modes_fwd: kv_dtype=%d", kv_dtype);
   DFD_REQUIRE(dfd_aligned16(k) && dfd_aligned16(q), "dfd_decoder_attn_modes_fwd: pointers must be 16-byte aligned");
   const size_t lds = (size_t)2 * T * patches * sizeof(float);
-  DFD_REQUIRE(lds <= 150 * 1024, "dfd_decoder_attn_modes_fwd: T*patches=%d too large for one LDS pass", T * patches);
+  // one ceiling for the pair: dfd_decoder_attn_modes_bwd keeps three floats per key, and a forward it cannot follow is refused
+  DFD_REQUIRE((size_t)3 * T * patches * sizeof(float) <= 150 * 1024,
+              "dfd_decoder_attn_modes_fwd: T*patches=%d too large for one LDS pass", T * patches);
   if (B == 0) return DFD_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
   // softmax-branch scores q_s·k/√d, -inf on padded frames (models.py:103-104); q holds [softmax | CoDA] per head

@@ -137,7 +137,9 @@ __global__ __launch_bounds__(MAXT) void decoder_attn_bwd_kernel(const float* __r
           dqs[e] = fmaf(dsu * 0.125f, kk, dqs[e]);
           dqc[e] = fmaf(dtu * 0.125f, kk, dqc[e]) + sg;
           sv[e] += sg;
-          dkk[e] = (dsu * qs[e] + dtu * qc[e]) * 0.125f - sg;
+          // which of the two products is fused is spelled out: left to the compiler, the bf16-output instantiation
+          // chose per channel, and its dk was not the f32 one rounded once
+          dkk[e] = fmaf(dtu, qc[e], dsu * qs[e]) * 0.125f - sg;
         }
         if (dk_out != nullptr) {
           const float wu = __shfl(w, lane_base + u, 64);
@@ -165,7 +167,7 @@ __global__ __launch_bounds__(MAXT) void decoder_attn_bwd_kernel(const float* __r
   // Σ_j (dK_j + dV_j) for this thread's 8 channels
   float dp[8];
 #pragma unroll
-  for (int e = 0; e < 8; ++e) dp[e] = (a1 * qs[e] + a2 * qc[e]) * 0.125f - sv[e] + a3 * dm[e];
+  for (int e = 0; e < 8; ++e) dp[e] = fmaf(a3, dm[e], fmaf(a2, qc[e], a1 * qs[e]) * 0.125f - sv[e]);  // fused as dkk is
 
   float* mine = red + ((size_t)rs * tpr + tr) * 24;
 #pragma unroll

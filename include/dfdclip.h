@@ -234,7 +234,9 @@ typedef struct {
  *   mix        f32 [B, heads*d]
  *   mix_softmax f32 [B, heads*d] or NULL: the softmax branch alone (Σ a_j v_j), kept for backward
  *   stats      f32 [B, heads, 2] = (row max, sum of exp) of the softmax branch, kept for backward
- *   workspace  f32, at least dfd_decoder_attn_workspace(B, heads, d, splits) bytes. */
+ *   workspace  f32, at least dfd_decoder_attn_workspace(B, heads, d, splits) bytes.
+ *   splits     workgroups per clip, 1..4096 with heads*splits <= 40928 (the merge keeps one float per (head, split) in
+ *              LDS); any count gives the same row max, splits past S stay empty. */
 size_t dfd_decoder_attn_workspace(int B, int heads, int d, int splits);
 int dfd_decoder_attn_fwd(const float* q, const void* k, const void* v, int kv_dtype, const dfd_kv_layout_t* layout,
                          const uint8_t* frame_mask, const float* ext_weights, float* mix, float* mix_softmax, float* stats,
@@ -245,7 +247,8 @@ int dfd_decoder_attn_fwd(const float* q, const void* k, const void* v, int kv_dt
  * "temporal" (over the frames at each patch position).  Writes scores [B, heads, S] = q_s·k/√d (-inf on
  * padded frames) and weights [B, heads, S] = Σ_modes softmax_mode(scores); pass `weights` to
  * dfd_decoder_attn_fwd as ext_weights (mix_softmax / stats are then not meaningful).  A group with
- * every key padded yields NaN, as in the reference. */
+ * every key padded yields NaN, as in the reference.  T*patches <= 12800 (one LDS pass per (clip, head); the backward
+ * keeps three floats per key there, and the forward refuses what the backward could not follow). */
 int dfd_decoder_attn_modes_fwd(const float* q, const void* k, int kv_dtype, const dfd_kv_layout_t* layout,
                                const uint8_t* frame_mask, int modes, float* scores, float* weights, int B, int T, int patches,
                                int heads, int d, void* stream);
