@@ -29,6 +29,8 @@ class DfdError(RuntimeError):
 
 GEMM_STREAM_OUT = 1
 GEMM_SPARE_IF_FREE = 2  # spare_cus is honoured only where it costs this shape no extra round of tiles
+GEMM_C_BLOCKED = 4  # C written / A read in the fragment-blocked layout of the MLP intermediate (blocked.py)
+GEMM_A_BLOCKED = 8
 
 
 class GemmExtra(Structure):
@@ -156,6 +158,9 @@ EXPLAIN_SIGNATURES = {
 # test / measurement hooks outside the ABI header (include/dfdclip_hooks.h)
 HOOK_SIGNATURES = {
     "dfd_attention_set_variant": (c_int, [c_int]),
+    "dfd_gemm_pair_set_variant": (c_int, [c_int]),
+    "dfd_gemm_pair_plan": (c_int, [c_int64, c_int, c_int]),
+    "dfd_gemm_pair_launches": (c_int64, []),
 }
 
 _lib = None
@@ -346,8 +351,11 @@ def profile_gemm_collect():
 
 
 def gemm(a, w, c, bias=None, epilogue=EPI_BIAS, m=None, pos=None, cls=None, k_export=None, v_export=None, tokens=0,
-         frames_per_clip=0, residual=None, qkv_first=0, drop=None, stream_out=False, spare_cus=0, tile_blocks=0, spare_if_free=False):
-    """c = epilogue(a[M,K] @ w[N,K]^T).  `m` limits the rows used (buffers may be over-allocated)."""
+         frames_per_clip=0, residual=None, qkv_first=0, drop=None, stream_out=False, spare_cus=0, tile_blocks=0, spare_if_free=False,
+         c_blocked=False, a_blocked=False):
+    """c = epilogue(a[M,K] @ w[N,K]^T).  `m` limits the rows used (buffers may be over-allocated).
+    `c_blocked` / `a_blocked`: the halves of a c_fc -> c_proj pair whose intermediate is kept fragment-blocked
+    (blocked.py; `w`, `bias` of the c_fc half are then the permuted copies, `blocked.fc_channel_perm`)."""
     _dev(a, w, c, bias, pos, cls, k_export, v_export, residual)
     assert a.dtype == w.dtype and a.stride(1) == 1 and w.stride(1) == 1 and c.stride(1) == 1
     M = a.shape[0] if m is None else m
@@ -356,9 +364,13 @@ def gemm(a, w, c, bias=None, epilogue=EPI_BIAS, m=None, pos=None, cls=None, k_ex
     assert residual is None or (residual.dtype == c.dtype and residual.stride(0) == c.stride(0))
     assert drop is None or epilogue == EPI_RESIDUAL_POS
     assert 0 <= epilogue <= EPI_BIAS_GELU, f"unknown epilogue {epilogue}"
+    if c_blocked or a_blocked:  # whole row groups of 16 behind the pointer
+        blk = c if c_blocked else a
+        assert blk.shape[0] >= (M + 15) // 16 * 16, "a blocked matrix needs its rows rounded up to 16"
     extra = GemmExtra(_ptr(pos).value, _ptr(cls).value, _ptr(k_export).value, _ptr(v_export).value, tokens, frames_per_clip,
                       _ptr(residual).value, qkv_first, drop.rng.data_ptr() if drop is not None and drop.p > 0 else None,
-                      drop.site if drop is not None else 0, drop.p if drop is not None else 0.0, (GEMM_STREAM_OUT if stream_out else 0) | (GEMM_SPARE_IF_FREE if spare_if_free else 0) | ((int(spare_cus) & 0xff) << 8) | ((int(tile_blocks) & 0xf) << 16))
+                      drop.site if drop is not None else 0, drop.p if drop is not None else 0.0, (GEMM_STREAM_OUT if stream_out else 0) | (GEMM_SPARE_IF_FREE if spare_if_free else 0) | ((int(spare_cus) & 0xff) << 8) | ((int(tile_blocks) & 0xf) << 16)
+                      | (GEMM_C_BLOCKED if c_blocked else 0) | (GEMM_A_BLOCKED if a_blocked else 0))
     timed = _profile["epilogue"] == epilogue
     if timed:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -401,6 +413,23 @@ def gemm_set_variant(variant):
     """0 = every GEMM kernel eligible, tiles dealt statically (default); 1 = skip the ping-pong kernel (tests / A-B runs);
     3 = the ping-pong kernel hands its tiles out dynamically (per-XCD counters).  Per thread.  Returns the previous value."""
     return load_library().dfd_gemm_set_variant(int(variant))
+
+
+def gemm_pair_set_variant(variant):
+    """The c_fc -> c_proj pair: 0 = fragment-blocked intermediate where `gemm_pair_plan` says so (default); 1 = row-major
+    everywhere (the A/B switch; a flagged call keeps its kernel and runs row-major); 2 = the plan also answers 1 below
+    1024 rows (tests).  Per thread.  Returns the previous value."""
+    return load_library().dfd_gemm_pair_set_variant(int(variant))
+
+
+def gemm_pair_plan(M, D, H):
+    """True where an MLP pair [M, D] -> [M, H] -> [M, D] on dense bf16 operands keeps its intermediate fragment-blocked."""
+    return bool(load_library().dfd_gemm_pair_plan(int(M), int(D), int(H)))
+
+
+def gemm_pair_launches():
+    """This thread's `gemm` launches so far that wrote or read a fragment-blocked matrix."""
+    return load_library().dfd_gemm_pair_launches()
 
 
 def gemm_last_path():

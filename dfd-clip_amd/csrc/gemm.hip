@@ -13,6 +13,7 @@
 // (r = lane&31, h = lane>>5) holds A[row r][k-slice h] and W[row r][k-slice h].
 #include "gemm_args.hpp"
 #include "gelu.hpp"
+#include "../../include/dfdclip_hooks.h"
 
 namespace {
 
@@ -308,6 +309,9 @@ static int fill_extra(GemmArgs& a, int epilogue, const dfd_gemm_extra* extra, in
     a.spare_cus = (int)((extra->flags >> DFD_GEMM_SPARE_CUS_SHIFT) & 0xff);
     a.spare_if_free = (extra->flags & DFD_GEMM_SPARE_IF_FREE) ? 1 : 0;
     a.tile_rows = 32 * (int)((extra->flags >> DFD_GEMM_TILE_BLOCKS_SHIFT) & 0xf);
+    a.c_blocked = (extra->flags & DFD_GEMM_C_BLOCKED) ? 1 : 0;
+    a.a_blocked = (extra->flags & DFD_GEMM_A_BLOCKED) ? 1 : 0;
+    a.pair = a.c_blocked | a.a_blocked;
     DFD_REQUIRE(a.tile_rows == 0 || a.tile_rows == 224 || a.tile_rows == 256, "dfd_gemm: tile blocks must be 0, 7 or 8");
     if (epilogue == DFD_EPI_RESIDUAL_POS && extra->drop_rng && extra->drop_p > 0.f) {
       DFD_REQUIRE(extra->drop_p < 1.f, "dfd_gemm: drop_p=%f", (double)extra->drop_p);
@@ -327,12 +331,53 @@ extern "C" int dfd_gemm_set_variant(int variant) {
   return old;
 }
 
+// ---- the c_fc -> c_proj pair with a fragment-blocked intermediate (gemm_blocked.hpp; hooks: include/dfdclip_hooks.h) ----
+static thread_local int g_pair_variant = 0;
+static thread_local int64_t g_pair_launches = 0;
+extern "C" int dfd_gemm_pair_set_variant(int variant) {
+  const int old = g_pair_variant;
+  g_pair_variant = variant;
+  return old;
+}
+extern "C" int64_t dfd_gemm_pair_launches(void) { return g_pair_launches; }
+// Both halves are put to the ping-pong kernel's own eligibility check (dfd_gemm256e_serves: the rules the launcher
+// applies to the flagged calls) as dense bf16 matrices at 16-byte aligned addresses, so the plan cannot promise what the
+// launcher refuses.  What the plan adds is policy: below 1,024 rows the pair stays with the kernels that serve small M
+// (variant 2 waives that, for tests), and the skip-the-ping-pong variant of dfd_gemm_set_variant leaves no kernel that
+// knows the layout.
+extern "C" int dfd_gemm_pair_plan(int64_t M, int D, int H) {
+  if (g_pair_variant == 1 || g_gemm_variant == 1 || M < 1 || D < 1 || H < 1) return 0;
+  if (M < 1024 && g_pair_variant != 2) return 0;
+  void* const any = reinterpret_cast<void*>(uintptr_t{256});  // an aligned address: nothing is dereferenced
+  GemmArgs fc{}, pr{};
+  fc.A = pr.A = any; fc.W = pr.W = any; fc.C = pr.C = any;
+  fc.M = pr.M = M; fc.pair = pr.pair = 1;
+  fc.N = H; fc.K = D; fc.lda = D; fc.ldw = D; fc.ldc = H; fc.c_blocked = 1;
+  pr.N = D; pr.K = H; pr.lda = H; pr.ldw = H; pr.ldc = D; pr.a_blocked = 1;
+  // (QuickGELU and the erf GELU share every rule that depends on the epilogue)
+  return dfd_gemm256e_serves(fc, DFD_BF16, DFD_EPI_BIAS_QUICKGELU) && dfd_gemm256e_serves(pr, DFD_BF16, DFD_EPI_BIAS) ? 1 : 0;
+}
+
 // The two persistent kernels in their order: gemm256e.hip (ping-pong K loop: K / step even and >= 6), then gemm256p.hip
 // (the other depths; variant 1 goes there at once).  0 = launched (*path = 257 / 256), <0 = error, 1 = neither serves it.
 static int try_persistent_kernels(GemmArgs& a, int c_dtype, int epilogue, bool f8, hipStream_t st, int* path) {
   // a q|k|v projection without an export is a plain biased store
   const int epi_p = epilogue == DFD_EPI_QKV_EXPORT && a.k_export == nullptr ? DFD_EPI_BIAS : epilogue;
   a.no_dynamic = g_gemm_variant != 3;
+  if (a.pair) {
+    // one half of a c_fc -> c_proj pair: this kernel or none (pair variant 1: the same kernel, row-major)
+    if (g_pair_variant == 1) a.c_blocked = a.a_blocked = 0;
+    *path = 257;
+    const int rc = f8 || g_gemm_variant == 1 ? 1 : dfd_gemm256e_try(a, c_dtype, epi_p, st);
+    if (rc == 1) {
+      dfd_set_error("dfd_gemm: DFD_GEMM_C_BLOCKED / DFD_GEMM_A_BLOCKED: the ping-pong kernel does not serve this call (bf16, N %% 256 == 0, "
+                    "K %% 128 == 0, K >= 384, ld %% 64 == 0, BIAS_QUICKGELU / BIAS_GELU for C, BIAS for A; got M=%lld N=%d K=%d)",
+                    (long long)a.M, a.N, a.K);
+      return DFD_ERR_INVALID_ARG;
+    }
+    if (rc == 0 && (a.c_blocked || a.a_blocked)) ++g_pair_launches;
+    return rc;
+  }
   int rc = g_gemm_variant == 1 ? 1 : (f8 ? dfd_gemm256e_f8_try : dfd_gemm256e_try)(a, c_dtype, epi_p, st);
   *path = 257;
   if (rc != 1) return rc;

@@ -36,6 +36,14 @@
 // each will have when the launch starts), so nothing is reset.  Captured launches keep the static order.  Measured on an
 // undisturbed chip: 0.4 % slower than the static order (profiles/r03_gemm_dynamic_vs_static_ab.txt), bit-identical.
 //
+// THE c_fc -> c_proj PAIR (gemm_blocked.hpp; DFD_GEMM_C_BLOCKED / DFD_GEMM_A_BLOCKED): the MLP intermediate has one reader,
+// this kernel's A loader, which forms every piece's source address itself.  So c_fc (activation epilogues) can store its
+// accumulator fragments where they are — the host permutes its output channels once so that a lane's fragments are 16
+// consecutive channels, and 2 RB wave-stores of 1 KB each replace the LDS round trip that turned fragments into rows — and
+// c_proj (plain epilogue) reads the same bytes back into the same LDS image: same instructions in the same order, other
+// addresses, every wait count unchanged.  Alone on the chip, interleaved with the row-major pair on this kernel
+// (tools/lab/pair_probe.py, profiles/gemm_blocked_pair_lab.txt): c_fc 0.413 -> 0.389 ms, c_proj 0.346 -> 0.348 ms, bit-identical.
+//
 // Measured on MI355X against gemm256p (same process, interleaved; profiles/r03_gemm_pingpong_lab.txt): c_fc 0.411 ->
 // 0.398-0.403 ms, q|k|v 0.285-0.292 -> 0.272-0.279, c_proj 0.388-0.395 -> 0.343-0.349, 8192^3 1,434 -> 1,590 TFLOP/s;
 // bit-identical to it on every shape; without the stagger (same code, groups in lockstep) 10-15 % slower.
@@ -50,7 +58,7 @@ constexpr int UNIT = 128 * ROWB;  // 16 KB: half of A (128 rows) or of W for one
 constexpr int DEPTH = 6;          // L segments between a unit's request and its read (4..6 measure the same; 6 tolerates the most latency)
 constexpr int NB = 2 * (DEPTH - 1);  // requests younger than the unit a segment waits for
 
-template <int EPI, int RB, bool F8, bool CF8>
+template <int EPI, int RB, bool F8, bool CF8, bool ABLK = false>
 __global__ __launch_bounds__(512) void gemm256e_kernel(const GemmArgs a, int tiles_m, int tiles_n) {
   static_assert(!F8 || RB == 8, "fp8 form: 256-row tiles only");
   static_assert(!CF8 || (F8 && EPI != DFD_EPI_QKV_EXPORT), "fp8 output: fp8 operands, plain, QuickGELU or GELU epilogue");
@@ -61,6 +69,12 @@ __global__ __launch_bounds__(512) void gemm256e_kernel(const GemmArgs a, int til
   constexpr int NCV = F8 ? 2 : 1;  // column-vector loads per wave and tile (bias; fp8: + column scales)
   constexpr int S1 = CF8 ? RB : 2 * RB;  // stores of an epilogue per wave (S2: a tile that also exports)
   constexpr int S2 = 4 * RB;
+  // the c_fc -> c_proj pair (gemm_blocked.hpp): the activation epilogues can WRITE C fragment-blocked (a flag of the launch
+  // says whether this one does); the plain one READS A fragment-blocked in an instantiation of its own (ABLK), so that
+  // the launches that share the plain form without reading the layout — q|k|v, out_proj — keep their code as it was
+  static_assert(!ABLK || (!F8 && EPI == DFD_EPI_BIAS), "blocked A: bf16 operands, plain epilogue");
+  constexpr bool C_BLK = !F8 && (EPI == DFD_EPI_BIAS_QUICKGELU || EPI == DFD_EPI_BIAS_GELU);
+  constexpr bool A_BLK = ABLK;
   __shared__ __attribute__((aligned(1024))) unsigned char smem[RING + 8 * STAGE];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -72,7 +86,7 @@ __global__ __launch_bounds__(512) void gemm256e_kernel(const GemmArgs a, int til
   const int xcd = bid & 7, q8 = G >> 3, r8 = G & 7;
   const int pos = xcd_position();
 
-  const OperandSrds<F8, CF8> srd(a);
+  const OperandSrds<F8, CF8, A_BLK, C_BLK> srd(a);
   const __amdgpu_buffer_rsrc_t srdA = srd.A, srdW = srd.W, srdC = srd.C;
   // descriptors of the column vectors as four plain words: their loads are inline asm
   const v4i srdB = words(a.bias ? a.bias : reinterpret_cast<const float*>(a.W), a.bias ? a.N * 4 : 0);
@@ -86,15 +100,28 @@ __global__ __launch_bounds__(512) void gemm256e_kernel(const GemmArgs a, int til
   // Rebuilt from an opaque copy of the lane id (nothing lane-dependent stays live across the tile loop for them).
   const uint32_t lda2 = (uint32_t)(a.lda * ESZ), ldw2 = (uint32_t)(a.ldw * ESZ);  // row pitches in bytes (ldw2 % 128 == 0)
   const uint32_t a_last = (uint32_t)(a.M - 1) * lda2;  // rows beyond M re-read the last valid row
+  // A fragment-blocked: the same pieces — LDS row 8 q + pr, position pp <- 16-byte chunk pp ^ ((4 q + (pr >> 1)) & 7) of
+  // that row's K tile — at the layout's addresses: each piece reads two runs of 512 bytes instead of eight 128-byte
+  // lines, and the K tile advances by a unit (2 KB) instead of a line.  The LDS image is the same byte for byte.
+  constexpr bool a_blk = A_BLK;
+  constexpr int a_kstep = a_blk ? (int)DFD_BLK_UNIT : ROWB;
   uint32_t vA[2][2], vW[2];
   auto set_a = [&](const Tile& t, int ha) {
     int l = lane;
     asm volatile("" : "+v"(l));
     const uint32_t pr = (uint32_t)(l >> 3), pp = (uint32_t)(l & 7);
-    const uint32_t ch0 = (pp ^ (pr >> 1)) << 4;  // source chunk of LDS position pp in row 8q + pr: pp ^ ((4q + (pr >> 1)) & 7)
-    const uint32_t row0 = ((uint32_t)t.m0 + (uint32_t)(WROWS * (wave >> 2) + 64 * ha + 16 * (wave & 3))) * lda2 + pr * lda2;
-    vA[ha][0] = min(row0, a_last) + ch0;
-    vA[ha][1] = min(row0 + 8u * lda2, a_last) + (ch0 ^ 64u);
+    if constexpr (a_blk) {
+      const uint32_t c0 = pp ^ (pr >> 1);
+      const uint32_t r0 = (uint32_t)t.m0 + (uint32_t)(WROWS * (wave >> 2) + 64 * ha + 16 * (wave & 3)) + pr;
+      const uint32_t m_last = (uint32_t)(a.M - 1);  // rows beyond M re-read the last valid row
+      vA[ha][0] = dfd_blk_row(min(r0, m_last), lda2) + dfd_blk_chunk(c0);
+      vA[ha][1] = dfd_blk_row(min(r0 + 8u, m_last), lda2) + dfd_blk_chunk(c0 ^ 4u);
+    } else {
+      const uint32_t ch0 = (pp ^ (pr >> 1)) << 4;  // source chunk of LDS position pp in row 8q + pr: pp ^ ((4q + (pr >> 1)) & 7)
+      const uint32_t row0 = ((uint32_t)t.m0 + (uint32_t)(WROWS * (wave >> 2) + 64 * ha + 16 * (wave & 3))) * lda2 + pr * lda2;
+      vA[ha][0] = min(row0, a_last) + ch0;
+      vA[ha][1] = min(row0 + 8u * lda2, a_last) + (ch0 ^ 64u);
+    }
   };
   auto set_w = [&](const Tile& t, int hb) {
     int l = lane;
@@ -109,8 +136,8 @@ __global__ __launch_bounds__(512) void gemm256e_kernel(const GemmArgs a, int til
   auto issue = [&](int kind, int kr) {
     unsigned char* d = smem + ((kind & 1) ? 0 : 4 * UNIT) + (2 * (kind >> 1) + (kr & 1)) * UNIT + wave * 16 * ROWB;
     if (kind & 1) {
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(srdA, (lds_ptr_t)d, 16, vA[kind >> 1][0], kr * ROWB, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(srdA, (lds_ptr_t)(d + 8 * ROWB), 16, vA[kind >> 1][1], kr * ROWB, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(srdA, (lds_ptr_t)d, 16, vA[kind >> 1][0], kr * a_kstep, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(srdA, (lds_ptr_t)(d + 8 * ROWB), 16, vA[kind >> 1][1], kr * a_kstep, 0, 0);
     } else {
       __builtin_amdgcn_raw_ptr_buffer_load_lds(srdW, (lds_ptr_t)d, 16, vW[kind >> 1], kr * ROWB, 0, 0);
       __builtin_amdgcn_raw_ptr_buffer_load_lds(srdW, (lds_ptr_t)(d + 8 * ROWB), 16, vW[kind >> 1] ^ 64u, kr * ROWB + 8 * (int)ldw2, 0, 0);
@@ -392,7 +419,7 @@ __global__ __launch_bounds__(512) void gemm256e_kernel(const GemmArgs a, int til
       if constexpr (F8) cs4[j] = *reinterpret_cast<const f32x4*>(ep + 256 + (j * 16 + (le >> 4) * 4) * 4);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // before the staging below overwrites them
-    const int stores = tile_epilogue<EPI, RB, F8, CF8>(a, acc, b4, cs4, ep, cur, wr, wc, le, D, srdC);
+    const int stores = tile_epilogue<EPI, RB, F8, CF8, C_BLK>(a, acc, b4, cs4, ep, cur, wr, wc, le, D, srdC);
     if (!has_next) break;
     s_prev = countable_stores<RB>(stores, cur, wr, a.M);
     idx = nidx;
@@ -458,6 +485,7 @@ bool sched_prepare(GemmArgs& a, hipStream_t st, int grid, int64_t ntiles) {
 struct Gemm256e {
   static constexpr const char* name = "ping-pong";
   static constexpr bool spare_if_free = true;
+  static constexpr bool blocked_layout = true;  // gemm_blocked.hpp
   static constexpr bool serves(int epi, bool f8) {
     return epi == DFD_EPI_BIAS || epi == DFD_EPI_BIAS_QUICKGELU || epi == DFD_EPI_BIAS_GELU || epi == DFD_EPI_QKV_EXPORT || (!f8 && epi == DFD_EPI_RESIDUAL_POS);
   }
@@ -472,7 +500,13 @@ struct Gemm256e {
   }
   template <int EPI, int RB, bool F8, bool CF8>
   static void run(int grid, hipStream_t st, const GemmArgs& a, int tiles_m, int tiles_n) {
-    hipLaunchKernelGGL((gemm256e_kernel<EPI, RB, F8, CF8>), dim3(grid), dim3(512), 0, st, a, tiles_m, tiles_n);
+    if constexpr (!F8 && EPI == DFD_EPI_BIAS) {
+      if (a.a_blocked) {  // c_proj reading the fragment-blocked `u`: the instantiation that knows the layout
+        hipLaunchKernelGGL((gemm256e_kernel<EPI, RB, F8, CF8, true>), dim3(grid), dim3(512), 0, st, a, tiles_m, tiles_n);
+        return;
+      }
+    }
+    hipLaunchKernelGGL((gemm256e_kernel<EPI, RB, F8, CF8, false>), dim3(grid), dim3(512), 0, st, a, tiles_m, tiles_n);
   }
 };
 
@@ -480,6 +514,9 @@ struct Gemm256e {
 
 // 0 = launched, <0 = error, 1 = shape / epilogue not served by this kernel
 int dfd_gemm256e_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st) { return try_persistent<Gemm256e, false>(a, c_dtype, epi, st); }
+
+// 1 = this kernel would serve the bf16 call (shape, leading dimensions, alignment, epilogue, layout flags); nothing is launched
+int dfd_gemm256e_serves(const GemmArgs& a, int c_dtype, int epi) { return persistent_serves<Gemm256e, false>(a, c_dtype, epi) == 0; }
 
 // fp8 (e4m3) operands on the block-scaled matrix cores; C bf16, or e4m3 for the plain / QuickGELU / GELU epilogues
 int dfd_gemm256e_f8_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st) { return try_persistent<Gemm256e, true>(a, c_dtype, epi, st); }

@@ -355,6 +355,7 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(const GemmArgs a, int til
 struct Gemm256p {
   static constexpr const char* name = "persistent";
   static constexpr bool spare_if_free = false;  // spare_cus is taken as given
+  static constexpr bool blocked_layout = false;  // gemm_blocked.hpp: gemm256e.hip's pair only
   static constexpr bool serves(int epi, bool f8) {
     return epi == DFD_EPI_BIAS || epi == DFD_EPI_BIAS_QUICKGELU || epi == DFD_EPI_QKV_EXPORT || (f8 && epi == DFD_EPI_BIAS_GELU);
   }

@@ -9,6 +9,7 @@
 #include "gemm_args.hpp"
 
 #include "gelu.hpp"
+#include "gemm_blocked.hpp"
 
 typedef int v4i_t __attribute__((ext_vector_type(4)));
 typedef v4i_t v4i;
@@ -88,11 +89,15 @@ __device__ __forceinline__ v4i words(const float* p, int bytes) {
   const uint64_t u = reinterpret_cast<uint64_t>(p);
   return v4i{(int)(uint32_t)u, (int)((uint32_t)(u >> 32) & 0xffffu), bytes, 0x00020000};
 }
-template <bool F8, bool CF8>
+// (ABLK / CBLK: the instantiation can read A / write C fragment-blocked, where the launch's flag says so)
+template <bool F8, bool CF8, bool ABLK = false, bool CBLK = false>
 struct OperandSrds {
   __amdgpu_buffer_rsrc_t A, W, C;
   __device__ __forceinline__ explicit OperandSrds(const GemmArgs& a)
-      : A(make_srd(a.A, a.M * a.lda * (F8 ? 1 : 2))), W(make_srd(a.W, (int64_t)a.N * a.ldw * (F8 ? 1 : 2))), C(make_srd(a.C, a.M * a.ldc * (CF8 ? 1 : 2))) {}
+      : A(make_srd(a.A, rows(a.M, ABLK && a.a_blocked) * a.lda * (F8 ? 1 : 2))), W(make_srd(a.W, (int64_t)a.N * a.ldw * (F8 ? 1 : 2))),
+        C(make_srd(a.C, rows(a.M, CBLK && a.c_blocked) * a.ldc * (CF8 ? 1 : 2))) {}
+  // a fragment-blocked matrix (gemm_blocked.hpp) keeps whole row groups: the rows of the last one reach to a multiple of 16
+  static __device__ __forceinline__ int64_t rows(int64_t M, bool blocked) { return blocked ? (M + 15) & ~(int64_t)15 : M; }
 };
 // The stores of a tile's epilogue that the wave may count in the next tile's first waits (gemm256e.hip's header has the
 // reason): all of them if all of the wave's rows are inside M, else none.
@@ -108,7 +113,9 @@ template <int RB> __device__ __forceinline__ int countable_stores(int stores, co
 // Every address below is rebuilt from an opaque copy of the lane id: left to itself the compiler hoists two dozen
 // tile-invariant address registers out of the tile loop and spills them (scratch traffic counts in vmcnt and would drain
 // the stores these kernels exist to leave in flight).
-template <int EPI, int RB, bool F8, bool CF8>
+// BLK: the instantiation also has the fragment-blocked form of the bf16 store (gemm_blocked.hpp), taken where
+// a.c_blocked says so: no staging at all, each lane stores its own fragments.
+template <int EPI, int RB, bool F8, bool CF8, bool BLK = false>
 __device__ __forceinline__ int tile_epilogue(const GemmArgs& a, f32x4 (&acc)[RB][4], const f32x4 (&b4)[4], const f32x4 (&cs4)[4], unsigned char* const ep,
                                              const Tile& cur, int wr, int wc, int le, int D, __amdgpu_buffer_rsrc_t srdC) {
   constexpr int WROWS = 16 * RB;  // rows per wave
@@ -309,6 +316,30 @@ __device__ __forceinline__ int tile_epilogue(const GemmArgs& a, f32x4 (&acc)[RB]
         store_out(d, srdC, off, a.stream_out);
       }
     }
+  } else if (BLK && a.c_blocked) {
+    // C fragment-blocked: the launcher permuted the output channels so that acc[i][0..3] of lane (er, eq) are channels
+    // 16 eq .. + 15 of row 16 i + er of this wave's 64; acc[i][2s], acc[i][2s + 1] are the 16-byte piece (s, er, eq) of
+    // unit (row group i, K tile nb / 64).  2 RB wave-stores of 1 KB of contiguous memory each: the count of the staged
+    // form, so every counted wait keeps its number.  No LDS write, no LDS read, no staging wait.
+    const int row0 = wr * WROWS + er;  // this lane's first row inside the tile (m0 is a multiple of 16)
+    const int rows_left_b = (int)min((int64_t)0x7fffffff, a.M - ((int64_t)cur.m0 + row0));
+    const uint32_t ldc2 = (uint32_t)(a.ldc * 2);
+    const uint32_t cbase = dfd_blk_row((uint32_t)cur.m0 + (uint32_t)row0, ldc2) + (uint32_t)(nb >> 6) * DFD_BLK_UNIT + (uint32_t)eq * 16u;
+#pragma unroll
+    for (int i = 0; i < RB; ++i) {
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const f32x4 v0 = activate(acc[i][2 * s]), v1 = activate(acc[i][2 * s + 1]);
+        bf16x8 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          o[e] = (bf16_t)v0[e];
+          o[4 + e] = (bf16_t)v1[e];
+        }
+        const uint32_t off = i * 16 < rows_left_b ? cbase + (uint32_t)i * (ldc2 * 16u) + (uint32_t)s * 1024u : 0xffffffffu;  // rows past M: dropped
+        store_out(__builtin_bit_cast(v4i, o), srdC, off, a.stream_out);
+      }
+    }
   } else {
     // C itself: 4 passes of 32 rows parked as bf16 (4 KB); 16 wave-stores of 8 rows x 128 B
     unsigned char* const park = ep + er * 128 + ((eq ^ ((er & 7) << 1)) << 3);  // + ii*2048, ^ (j << 5)
@@ -407,13 +438,17 @@ int launch_persistent(const GemmArgs& a_in, hipStream_t st) {
 
 // eligibility common to both kernels: 0 = fine, 1 = not served.  (Each adds its own rule for the K depth: L::depth_ok.)
 inline int check_persistent(const GemmArgs& a, int esz, int csz, int kstep) {
-  if (a.N % TN != 0 || a.K % kstep != 0 || a.M < 1024) return 1;
+  if (a.N % TN != 0 || a.K % kstep != 0 || (a.M < 1024 && !a.pair)) return 1;  // (one half of a c_fc -> c_proj pair: any M)
   if ((a.lda * esz) % 16 != 0 || (a.ldw * esz) % 16 != 0 || (a.ldc * csz) % 16 != 0) return 1;
   if ((reinterpret_cast<uintptr_t>(a.A) & 15) != 0 || (reinterpret_cast<uintptr_t>(a.W) & 15) != 0 || (reinterpret_cast<uintptr_t>(a.C) & 15) != 0) return 1;
   if (a.bias && (reinterpret_cast<uintptr_t>(a.bias) & 15) != 0) return 1;
   const int64_t lim = (int64_t)0xfffffff0;  // buffer descriptors carry 32-bit byte offsets
-  if (a.M * a.lda * esz > lim || (int64_t)a.N * a.ldw * esz > lim || a.M * a.ldc * csz > lim) return 1;
+  const int64_t Mr = a.pair ? (a.M + 15) & ~(int64_t)15 : a.M;  // a blocked matrix keeps whole groups of 16 rows
+  if (Mr * a.lda * esz > lim || (int64_t)a.N * a.ldw * esz > lim || Mr * a.ldc * csz > lim) return 1;
   if ((int64_t)((a.M + 223) / 224) * (a.N / TN) > 0x3fffffff || a.M >= ((int64_t)1 << 31)) return 1;
+  // the fragment-blocked layout (gemm_blocked.hpp): bf16, whole 64-channel K tiles in every row group
+  if ((a.c_blocked || a.a_blocked) && (esz != 2 || csz != 2)) return 1;
+  if ((a.c_blocked && a.ldc % 64 != 0) || (a.a_blocked && a.lda % 64 != 0)) return 1;
   return 0;
 }
 
@@ -433,13 +468,28 @@ inline int check_residual_pos(const GemmArgs& a) {
 
 // (epi, c_dtype, F8) -> an instantiation of kernel family L, where L serves it: 0 = launched, <0 = error, 1 = shape /
 // epilogue not served.  fp8 operands: C bf16, or e4m3 for the plain / QuickGELU / GELU epilogues.
+// The shape / layout rules of kernel family L for a call, without launching anything: 0 = fine, 1 = not served.  The
+// first thing try_persistent asks, and what the host's plan of a c_fc -> c_proj pair asks for both halves (gemm.hip,
+// dfd_gemm_pair_plan), so that the plan cannot say yes to a call the launcher then refuses.
 template <class L, bool F8>
-int try_persistent(const GemmArgs& a_in, int c_dtype, int epi, hipStream_t st) {
+int persistent_serves(const GemmArgs& a_in, int c_dtype, int epi) {
   if (c_dtype != DFD_BF16 && !(F8 && c_dtype == DFD_FP8)) return 1;
   const bool cf8 = c_dtype == DFD_FP8;
   constexpr int esz = F8 ? 1 : 2, kstep = F8 ? 128 : TK;
   if (F8 && (!a_in.col_scale || (reinterpret_cast<uintptr_t>(a_in.col_scale) & 15) != 0)) return 1;
   if (check_persistent(a_in, esz, cf8 ? 1 : 2, kstep) || !L::depth_ok(a_in, esz, a_in.K / kstep, epi)) return 1;
+  if (!L::serves(epi, F8)) return 1;
+  // blocked C: the MLP's activation epilogues write it; blocked A: the plain epilogue reads it (L::blocked_layout)
+  if ((a_in.c_blocked || a_in.a_blocked) && !L::blocked_layout) return 1;
+  if (a_in.c_blocked && epi != DFD_EPI_BIAS_QUICKGELU && epi != DFD_EPI_BIAS_GELU) return 1;
+  if (a_in.a_blocked && epi != DFD_EPI_BIAS) return 1;
+  return 0;
+}
+
+template <class L, bool F8>
+int try_persistent(const GemmArgs& a_in, int c_dtype, int epi, hipStream_t st) {
+  if (persistent_serves<L, F8>(a_in, c_dtype, epi)) return 1;
+  const bool cf8 = c_dtype == DFD_FP8;
   GemmArgs a = a_in;
   auto go = [&](auto epi_c) -> int {
     constexpr int EPI = decltype(epi_c)::value;

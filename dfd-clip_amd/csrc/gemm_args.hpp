@@ -30,11 +30,16 @@ struct GemmArgs {
   uint32_t* sched;
   uint32_t sched_base[8];
   int no_dynamic;  // tests / A-B: 1 = keep the static order
+  // gemm256e.hip, the c_fc -> c_proj pair (gemm_blocked.hpp): C is written / A is read in the fragment-blocked layout.
+  // pair: the call is one half of such a pair (DFD_GEMM_C_BLOCKED / DFD_GEMM_A_BLOCKED) — gemm256e.hip serves it, at any
+  // M, or it is an error; dfd_gemm_pair_set_variant(1) keeps `pair` and clears the other two (the row-major pair).
+  int c_blocked, a_blocked, pair;
 };
 
 // tuned kernels: 0 = launched, <0 = error, 1 = shape / epilogue not eligible
 int dfd_gemm256_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st);      // gemm256.hip: one workgroup per tile
 int dfd_gemm256e_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st);     // gemm256e.hip: persistent, ping-pong K loop (tried first)
+int dfd_gemm256e_serves(const GemmArgs& a, int c_dtype, int epi);                   // ... would it serve the bf16 call? 1 = yes (no launch)
 int dfd_gemm256e_f8_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st);  // same kernel, e4m3 operands (dfd_gemm_fp8)
 int dfd_gemm256p_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st);     // gemm256p.hip: persistent, the K depths gemm256e does not serve
 int dfd_gemm256p_f8_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st);  // same kernel, e4m3 operands

@@ -37,7 +37,7 @@ import contextlib
 import torch
 from torch import nn
 
-from . import capi
+from . import blocked, capi
 
 
 FP8_PRESETS = ("all", "proj-bf16", "kv-bf16", "kv+proj-bf16", "edges-bf16", "none")
@@ -366,7 +366,28 @@ class VisionTransformer(RuntimeStateMixin, nn.Module):
         if dev.type != "cuda":
             raise capi.DfdError("the encoder runs on HIP kernels only: move the model to a GPU (.to('cuda'))")
         self._prepared = self._stage(dev)
+        self._stage_blocked_fc(self._prepared)
         return self._prepared
+
+    def _stage_blocked_fc(self, p):
+        """c_fc's weight rows and bias with the output channels permuted for the fragment-blocked `u` (blocked.py,
+        csrc/gemm_blocked.hpp), in the prepared copies only: the operands of the c_fc -> c_proj pair where `_pair_blocked`
+        says the pair runs.  Every channel's dot product is unchanged; the channel just comes out of another MFMA column."""
+        if self.act_dtype != torch.bfloat16:
+            return
+        for bp in p["blocks"]:
+            H = bp["w_fc"].shape[0]
+            if H % 64 == 0 and bp["w_proj"].shape[1] == H:
+                idx = blocked.fc_channel_perm(H, device=bp["w_fc"].device)
+                bp["w_fc_blk"], bp["b_fc_blk"] = bp["w_fc"][idx].contiguous(), bp["b_fc"][idx].contiguous()
+
+    def _pair_blocked(self, bp, M, pl=_NONE):
+        """Whether this layer's c_fc -> c_proj pair keeps `u` fragment-blocked for a pass over M rows: both halves on bf16
+        operands (not the e4m3 c_fc, whatever c_proj reads), and the library's plan for the shapes (`capi.gemm_pair_plan`:
+        both GEMMs on the ping-pong kernel, the A/B switch).  Decided here and nowhere else on the Python side."""
+        if "w_fc_blk" not in bp or not self.deferred_residual or pl["fc"] == "fp8" or pl["proj"] == "fp8":
+            return False
+        return capi.gemm_pair_plan(M, self.width, bp["w_fc"].shape[0])
 
     def _stage(self, dev):
         """Device-side operands of the kernels, derived from the parameters (rebuilt after they change)."""
@@ -516,7 +537,7 @@ class VisionTransformer(RuntimeStateMixin, nn.Module):
                                     delta2=ws["delta2"][:M] if pend == 2 else None, store_x=not discard_x)
             ws["pending"] = 0
 
-    def _residual(self, ws, a, w, b, M, spare_cus=0, spare_if_free=False):
+    def _residual(self, ws, a, w, b, M, spare_cus=0, spare_if_free=False, a_blocked=False):
         """x = x + Linear(a) (model.py:222-223).  fp32 path: read-modify-write of x in the GEMM
         epilogue.  bf16 path: the GEMM stores its output as a bf16 delta (plain store epilogue, a
         quarter of the epilogue bytes) and the add is deferred to the LayerNorm that follows."""
@@ -524,7 +545,7 @@ class VisionTransformer(RuntimeStateMixin, nn.Module):
             pend = ws.get("pending", 0)
             assert pend < 2
             capi.gemm(a, w, ws["delta2" if pend else "delta"], b, capi.EPI_BIAS, m=M, stream_out=self.stream_out["proj" if pend else "out"],
-                      spare_cus=spare_cus, spare_if_free=spare_if_free)
+                      spare_cus=spare_cus, spare_if_free=spare_if_free, a_blocked=a_blocked)
             ws["pending"] = pend + 1
         else:
             capi.gemm(a, w, ws["x"], b, capi.EPI_BIAS_RESIDUAL, m=M)
@@ -599,10 +620,18 @@ class VisionTransformer(RuntimeStateMixin, nn.Module):
             self._ln(ws, bp["ln2"], M, store=False)
             if calib is not None:
                 calib.append(ws["h"][:M].abs().max())
-            capi.gemm(ws["h"], bp["w_fc"], ws["u"], bp["b_fc"], self.act_epilogue, m=M, stream_out=so["fc"], spare_cus=sp_fc, spare_if_free=free)
+            # `u` fragment-blocked between the two (c_fc stores its accumulator fragments as they are, c_proj's loader
+            # restores the rows on the way into LDS): same values, other places.  Anything else that reads `u` by position
+            # goes through blocked.unpack.
+            blk = self._pair_blocked(bp, M, pl)
+            w_fc, b_fc = (bp["w_fc_blk"], bp["b_fc_blk"]) if blk else (bp["w_fc"], bp["b_fc"])
+            capi.gemm(ws["h"], w_fc, ws["u"], b_fc, self.act_epilogue, m=M, stream_out=so["fc"], spare_cus=sp_fc, spare_if_free=free,
+                      c_blocked=blk)
             if calib is not None:
-                calib.append(ws["u"][:M].abs().max())
-            self._residual(ws, ws["u"], bp["w_proj"], bp["b_proj"], M, spare_cus=sp_proj, spare_if_free=free)
+                # (blocked: the first M rows' bytes are not the first M rows.  Through unpack, so that what an earlier
+                # row-major pass over this workspace left in the never-written pieces of the last group stays out)
+                calib.append((blocked.unpack(ws["u"][:blocked.padded_rows(M)], M) if blk else ws["u"][:M]).abs().max())
+            self._residual(ws, ws["u"], bp["w_proj"], bp["b_proj"], M, spare_cus=sp_proj, spare_if_free=free, a_blocked=blk)
 
     @torch.no_grad()
     def forward(self, x, with_out=False, with_q=False):

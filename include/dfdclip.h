@@ -91,6 +91,13 @@ enum {
                                tiles for this shape (ViT-B/16's c_proj: 5 rounds on 224 CUs as on 256; ViT-L/14's: 5 instead
                                of 4, so there the kernel takes every CU).  Without the bit the request is binding (the
                                window a collective needs beside the encoder) */
+  DFD_GEMM_C_BLOCKED = 4,   /* dfd_gemm, bf16, BIAS_QUICKGELU / BIAS_GELU: C is written in the fragment-blocked layout of the
+                               MLP intermediate (dfd-clip_amd/csrc/gemm_blocked.hpp; dfd-clip_amd/blocked.py packs and
+                               unpacks it) and W, bias are taken with their output channels permuted for it
+                               (blocked.fc_channel_perm).  C needs M rounded up to 16 rows and ldc % 64 == 0 */
+  DFD_GEMM_A_BLOCKED = 8,   /* dfd_gemm, bf16, BIAS: A is read in that layout (lda % 64 == 0).  A call with either bit is
+                               one half of a c_fc -> c_proj pair: the ping-pong persistent kernel serves it, at any M, or
+                               the call fails (no other kernel knows the layout) */
   DFD_GEMM_TILE_BLOCKS_SHIFT = 16, /* bits 16..19: 0 = the persistent kernel chooses its tile height; 7 / 8 = force 224- /
                                256-row tiles (tests, tuning) */
   DFD_GEMM_SPARE_CUS_SHIFT = 8 /* bits 8..15: compute units the persistent kernel leaves free (its grid is one workgroup

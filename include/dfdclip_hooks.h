@@ -4,6 +4,8 @@
 #ifndef DFDCLIP_HOOKS_H
 #define DFDCLIP_HOOKS_H
 
+#include <stdint.h>
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -14,6 +16,20 @@ extern "C" {
  * the streaming bf16 MFMA kernel (attention_mfma_any.hip), so that the rows kernel serves the token counts outside the
  * 193..224 and 257..288 windows as it did before that kernel existed.  Per thread; returns the previous value. */
 int dfd_attention_set_variant(int variant);
+
+/* The c_fc -> c_proj pair of the encoder's MLP (DFD_GEMM_C_BLOCKED / DFD_GEMM_A_BLOCKED).  0 (default) = the pair keeps
+ * the intermediate fragment-blocked where dfd_gemm_pair_plan says so; 1 = row-major everywhere: the plan answers 0 and a
+ * call that carries one of the bits runs on the same kernel with a row-major C / A (the bits then only waive the
+ * M >= 1024 rule) — the A/B switch; 2 = the plan also answers 1 below 1024 rows (tests: two frames are enough to cross a
+ * ragged panel).  Per thread; returns the previous value. */
+int dfd_gemm_pair_set_variant(int variant);
+/* 1 = an MLP pair u[M, H] = act(h[M, D] . Wfc^T), delta[M, D] = u . Wproj^T on bf16 operands with dense rows runs both
+ * halves on the ping-pong kernel and keeps u fragment-blocked (the caller then sets the two bits and passes the permuted
+ * c_fc weights); 0 = the row-major pair.  The one place that decides it. */
+int dfd_gemm_pair_plan(int64_t M, int D, int H);
+/* The number of this thread's dfd_gemm calls so far that wrote or read a fragment-blocked matrix (served with
+ * DFD_GEMM_C_BLOCKED or DFD_GEMM_A_BLOCKED in force; not the calls variant 1 turned row-major).  For tests. */
+int64_t dfd_gemm_pair_launches(void);
 
 #ifdef __cplusplus
 }
