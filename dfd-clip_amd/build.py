@@ -70,6 +70,7 @@ def build(force=False, verbose=False, extra_flags=()):
     headers.append(os.path.join(INCLUDE, "dfdclip.h"))
     headers.append(os.path.join(INCLUDE, "dfdclip_ext.h"))
     headers.append(os.path.join(INCLUDE, "dfdclip_explain.h"))
+    headers.append(os.path.join(INCLUDE, "dfdclip_augment.h"))
     headers.append(os.path.join(INCLUDE, "dfdclip_hooks.h"))
     jobs, objs = [], []
     for src in sources():

@@ -6,7 +6,7 @@ raises.  Tensors are passed as raw device pointers; every call enqueues on
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint8, c_uint32, c_void_p
 
 import torch
 
@@ -155,6 +155,21 @@ EXPLAIN_SIGNATURES = {
                                      c_int, c_int, c_int, c_void_p]),
 }
 
+
+class AugmentSet(Structure):
+    """dfd_augment_set_t (include/dfdclip_augment.h): one draw of the training augmentation."""
+    _fields_ = [("flags", c_uint32), ("hue", c_int32), ("sat", c_int32), ("val", c_int32), ("quality", c_int32),
+                ("reserved", c_int32 * 3), ("rgb_lut", (c_uint8 * 256) * 3), ("tone_lut", c_uint8 * 256)]
+
+
+AUG_RGB_LUT, AUG_HSV, AUG_TONE_LUT, AUG_FLIP = 1, 2, 4, 8
+AUGMENT_SET_BYTES = ctypes.sizeof(AugmentSet)  # the header documents it as DFD_AUGMENT_SET_BYTES
+
+# training augmentation beside the ABI, in a header of its own (include/dfdclip_augment.h)
+AUGMENT_SIGNATURES = {
+    "dfd_augment_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+}
+
 # test / measurement hooks outside the ABI header (include/dfdclip_hooks.h)
 HOOK_SIGNATURES = {
     "dfd_attention_set_variant": (c_int, [c_int]),
@@ -177,7 +192,7 @@ def load_library(path=None):
     if not os.path.exists(path):
         raise DfdError(f"{path} not found: the HIP kernel library is not built and there is no fallback path")
     lib = ctypes.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **EXPLAIN_SIGNATURES, **HOOK_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **EXPLAIN_SIGNATURES, **AUGMENT_SIGNATURES, **HOOK_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError:
@@ -324,6 +339,21 @@ def preprocess_u8(frames, out, res, patch, mean, std, antialias=True, patch_rows
         kpad = 0
     _check(load_library().dfd_preprocess_u8(_ptr(frames), n, h, w, res, patch, int(bool(antialias)), m3, s3, _ptr(out),
                                             _DTYPE[out.dtype], 1 if patch_rows else 0, kpad, _stream()), "dfd_preprocess_u8")
+    return out
+
+
+def augment_u8(frames, out, sets, set_of_frame):
+    """out[f] = the augmentation `sets[set_of_frame[f]]` of frames[f] (include/dfdclip_augment.h); frames, out u8
+    [n,3,H,W] (distinct), sets u8 [n_sets, AUGMENT_SET_BYTES] = dfd_augment_set_t records, set_of_frame i32 [n]; an index outside
+    [0, n_sets) copies the frame.  The device-side colour / JPEG / flip presets of reference `src/datasets.py:288-399`."""
+    _dev(frames, out, sets, set_of_frame)
+    assert frames.dtype == torch.uint8 and out.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[1] == 3
+    assert frames.is_contiguous() and out.is_contiguous() and out.shape == frames.shape
+    assert sets.dtype == torch.uint8 and sets.is_contiguous() and sets.dim() == 2 and sets.shape[1] == AUGMENT_SET_BYTES
+    n, _, h, w = frames.shape
+    assert set_of_frame.dtype == torch.int32 and set_of_frame.is_contiguous() and set_of_frame.numel() == n
+    _check(load_library().dfd_augment_u8(_ptr(frames), _ptr(out), n, h, w, _ptr(sets), sets.shape[0], _ptr(set_of_frame), _stream()),
+           "dfd_augment_u8")
     return out
 
 

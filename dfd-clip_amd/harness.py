@@ -5,7 +5,9 @@ code, so that a reference user finds the same step semantics on top of `Detector
 
   train_step      `Trainer.run`'s loop body (`src/trainer.py:108-177`): zero_grad -> for each training
                   set: forward(train=True, single_task=idx) -> backward(task_loss[idx].mean() + Σ other)
-                  -> [gradient all-reduce] -> optimizer.step -> lr_scheduler.step.
+                  -> [gradient all-reduce] -> optimizer.step -> lr_scheduler.step.  `augment=`: the datasets'
+                  colour / JPEG / flip augmentation (`src/datasets.py:288-399`) applied to each batch's uint8 device
+                  clips first (`augment.ClipAugment`).
   make_one_cycle  the OneCycleLR the trainer builds (`src/trainer.py:51-60`): initial lr = max/25 and
                   `total_steps = max_steps * num_processes` because Accelerate steps a prepared
                   scheduler once per process per optimizer step; `step_scheduler` mirrors that.
@@ -70,11 +72,22 @@ class EmaTeacher:
         return [labels if i == task_index else teacher_logits[i].softmax(dim=-1) for i in range(total_tasks)]
 
 
-def train_step(model, optimizer, batches, scheduler=None, total_tasks=None, teacher=None):
+def _augmented(frames, augment):
+    """The batch's frames through `augment` (an `augment.ClipAugment`): uint8 device clips only, since the augmentation
+    is defined on 8-bit samples and runs on the GPU."""
+    if not (torch.is_tensor(frames) and frames.is_cuda and frames.dtype == torch.uint8):
+        raise TypeError("augment= needs uint8 device frames [B,T,3,H,W]; got "
+                        f"{getattr(frames, 'dtype', type(frames))} on {getattr(frames, 'device', 'the host')}")
+    return augment(frames)
+
+
+def train_step(model, optimizer, batches, scheduler=None, total_tasks=None, teacher=None, augment=None):
     """One optimizer step over `batches`: list of (frames, labels, mask, comps, speed, task_index)
     — one entry per training set, as the reference draws one batch per set per step.
     With an `EmaTeacher` that has started teaching, every task contributes a loss (the other tasks
     against the teacher's soft labels); the teacher is updated after the optimizer step.
+    `augment`: an `augment.ClipAugment`; each batch's uint8 device frames go through it (one fresh draw per batch) before
+    the model and the teacher see them, as the reference's datasets augment before collation.
     Returns {"losses": [...per batch mean task loss...], "logits": [...]}."""
     total_tasks = total_tasks or len(model.out_dim)
     model.zero_grad()
@@ -82,6 +95,8 @@ def train_step(model, optimizer, batches, scheduler=None, total_tasks=None, teac
     out = {"losses": [], "logits": []}
     teaching = teacher is not None and teacher.teaching
     for frames, labels, mask, comps, speed, task_index in batches:
+        if augment is not None:
+            frames = _augmented(frames, augment)
         if teaching:
             y_list = teacher.labels(frames, mask, labels, task_index, total_tasks)
         else:
@@ -105,13 +120,16 @@ def train_step(model, optimizer, batches, scheduler=None, total_tasks=None, teac
     return out
 
 
-def compinv_train_step(model, optimizer, batches, scheduler=None):
-    """One `CompInvTrainer` step for a `CompInvEncoder`: `batches` = list of (frames, comp), one per training set.
+def compinv_train_step(model, optimizer, batches, scheduler=None, augment=None):
+    """One `CompInvTrainer` step for a `CompInvEncoder`: `batches` = list of (frames, comp), one per training set;
+    `augment` as for `train_step`.
     Returns {"recon": [...], "match": [...]}, detached 0-dim device tensors per batch."""
     model.zero_grad()
     model.train()
     out = {"recon": [], "match": []}
     for frames, comp in batches:
+        if augment is not None:
+            frames = _augmented(frames, augment)
         recon, match = model(frames, comp)
         (recon + match).backward()
         out["recon"].append(recon.detach())
