@@ -6,7 +6,7 @@ raises.  Tensors are passed as raw device pointers; every call enqueues on
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint8, c_uint32, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint, c_uint8, c_uint32, c_void_p
 
 import torch
 
@@ -176,7 +176,13 @@ HOOK_SIGNATURES = {
     "dfd_gemm_pair_set_variant": (c_int, [c_int]),
     "dfd_gemm_pair_plan": (c_int, [c_int64, c_int, c_int]),
     "dfd_gemm_pair_launches": (c_int64, []),
+    "dfd_stream_policy_set": (c_uint, [c_uint]),
+    "dfd_stream_policy_get": (c_uint, []),
 }
+
+# families of dfd_stream_policy_set (include/dfdclip_hooks.h)
+STREAM_DECODER_KV, STREAM_DECODER_WEIGHTS, STREAM_OPTIMIZER, STREAM_ENCODER_ROWS, STREAM_ALL = 1, 2, 4, 8, 15
+STREAM_DEFAULT = STREAM_DECODER_KV | STREAM_ENCODER_ROWS
 
 _lib = None
 
@@ -460,6 +466,17 @@ def gemm_pair_plan(M, D, H):
 def gemm_pair_launches():
     """This thread's `gemm` launches so far that wrote or read a fragment-blocked matrix."""
     return load_library().dfd_gemm_pair_launches()
+
+
+def stream_policy_set(mask):
+    """Which kernel families issue their read-once loads / write-once stores non-temporally (STREAM_* bits; results are
+    bit-identical either way).  Process-wide, read at launch: a captured graph keeps what was set at capture.  Returns the
+    previous mask."""
+    return load_library().dfd_stream_policy_set(int(mask))
+
+
+def stream_policy_get():
+    return load_library().dfd_stream_policy_get()
 
 
 def gemm_last_path():

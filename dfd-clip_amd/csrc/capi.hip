@@ -1,6 +1,7 @@
 // Error string, version and device check of the C ABI (include/dfdclip.h).
-#include "common.hpp"
+#include "stream_policy.hpp"
 #include <string.h>
+#include <atomic>
 
 static thread_local char g_err[512] = "";
 
@@ -13,6 +14,13 @@ void dfd_set_error(const char* fmt, ...) {
 
 extern "C" const char* dfd_last_error(void) { return g_err; }
 extern "C" int dfd_abi_version(void) { return DFD_ABI_VERSION; }
+
+// process-wide, not per thread like the kernel-variant hooks: autograd launches the backward kernels from its own thread
+static std::atomic<unsigned> g_stream_policy{DFD_STREAM_DEFAULT};
+
+extern "C" unsigned dfd_stream_policy_set(unsigned mask) { return g_stream_policy.exchange(mask & DFD_STREAM_ALL); }
+extern "C" unsigned dfd_stream_policy_get(void) { return g_stream_policy.load(); }
+bool dfd_stream_on(unsigned family_bit) { return (g_stream_policy.load(std::memory_order_relaxed) & family_bit) != 0; }
 
 extern "C" int dfd_device_check(void) {
   int dev = 0;

@@ -22,7 +22,7 @@ namespace {
 constexpr int HD = 64;
 constexpr int PART = 2 + 2 * HD;  // floats per (clip, split, head): m, l, acc_s[64], acc_c[64]
 
-template <typename T, int MAXT, bool POS>
+template <typename T, int MAXT, bool POS, bool NT>
 __global__ __launch_bounds__(MAXT, (MAXT <= 512 ? (POS ? 2 : 3) : 4)) void decoder_attn_partial_kernel(const float* __restrict__ q, const T* __restrict__ k,
                                                                     const T* __restrict__ v,
                                                                     const uint8_t* __restrict__ frame_mask,
@@ -86,8 +86,8 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 512 ? (POS ? 2 : 3) : 4)) void decod
       const int s = min(min(s0 + u * R, s_end - 1), S - 1);  // clamp: rows past the end are loaded but not used
       const int tf = (int)div_patches.div((uint32_t)s);
       const int64_t off = (int64_t)tf * lay.frame_stride + (int64_t)(s - tf * patches) * lay.row_stride;
-      kr[u].load(kb + off);
-      vr[u].load(vb + off);
+      kr[u].template load<NT>(kb + off);
+      vr[u].template load<NT>(vb + off);
       po[u] = (tf - f0) * D;
     }
     float pds[UN], pdc[UN], pl1[UN];
@@ -298,7 +298,7 @@ __global__ __launch_bounds__(256) void decoder_modes_fwd_kernel(const float* __r
   for (int i = threadIdx.x; i < S; i += 256) weights[base + i] = aw[i];
 }
 
-template <int EPI>
+template <int EPI, bool NT>
 __global__ __launch_bounds__(256) void linear_rows_kernel(const float* __restrict__ x, int64_t ldx,
                                                           const float* __restrict__ W, const float* __restrict__ bias,
                                                           float* __restrict__ y, int64_t ldy, int B, int N, int K) {
@@ -311,7 +311,7 @@ __global__ __launch_bounds__(256) void linear_rows_kernel(const float* __restric
 #pragma unroll
     for (int i = 0; i < 8; ++i) acc[i] = 0.f;
     for (int kk = lane * 4; kk < K; kk += 256) {
-      const f32x4 w4 = *reinterpret_cast<const f32x4*>(wr + kk);
+      const f32x4 w4 = stream_load16<NT>(wr + kk);  // the weight row: read once (DFD_STREAM_DECODER_WEIGHTS)
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         if (b0 + i < B) {
@@ -392,6 +392,7 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ x, 
 // order (deterministic) and applies bias / QuickGELU / residual.
 constexpr int LT_TILE = 256;  // output columns per workgroup
 
+template <bool NT>  // the Wt rows are read once (DFD_STREAM_DECODER_WEIGHTS); the slabs the reduce re-reads at once stay plain
 __global__ __launch_bounds__(256) void linear_t_partial_kernel(const float* __restrict__ x, int64_t ldx,
                                                                const float* __restrict__ Wt, float* __restrict__ part, int B,
                                                                int N, int K, int rows_per_wave) {
@@ -410,7 +411,7 @@ __global__ __launch_bounds__(256) void linear_t_partial_kernel(const float* __re
     for (; k + 8 <= k1; k += 8) {  // 8 independent 1 KB row reads in flight per wave
       f32x4 w[8];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) w[u] = *reinterpret_cast<const f32x4*>(wp + (int64_t)(k + u) * N);
+      for (int u = 0; u < 8; ++u) w[u] = stream_load16<NT>(wp + (int64_t)(k + u) * N);
 #pragma unroll
       for (int u = 0; u < 8; ++u)
 #pragma unroll
@@ -418,7 +419,7 @@ __global__ __launch_bounds__(256) void linear_t_partial_kernel(const float* __re
           if (b < B) acc[b] += w[u] * x[(int64_t)b * ldx + k + u];
     }
     for (; k < k1; ++k) {
-      const f32x4 w = *reinterpret_cast<const f32x4*>(wp + (int64_t)k * N);
+      const f32x4 w = stream_load16<NT>(wp + (int64_t)k * N);
 #pragma unroll
       for (int b = 0; b < 16; ++b)
         if (b < B) acc[b] += w * x[(int64_t)b * ldx + k];
@@ -529,13 +530,18 @@ extern "C" int dfd_decoder_attn_fwd(const float* q, const void* k, const void* v
   hipStream_t st = static_cast<hipStream_t>(stream);
   const dim3 grid(splits, B), block(threads);
   float* ws = static_cast<float*>(workspace);
-#define PARTIAL_LAUNCH1(KT, MT, PS)                                                                                  \
+  const bool nt = dfd_stream_on(DFD_STREAM_DECODER_KV);
+#define PARTIAL_LAUNCH2(KT, MT, PS, NT)                                                                              \
   do {                                                                                                               \
     if (lds > 64 * 1024)                                                                                             \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&decoder_attn_partial_kernel<KT, MT, PS>),              \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&decoder_attn_partial_kernel<KT, MT, PS, NT>),          \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                               \
-    hipLaunchKernelGGL((decoder_attn_partial_kernel<KT, MT, PS>), grid, block, lds, st, q, static_cast<const KT*>(k), \
+    hipLaunchKernelGGL((decoder_attn_partial_kernel<KT, MT, PS, NT>), grid, block, lds, st, q, static_cast<const KT*>(k), \
                        static_cast<const KT*>(v), frame_mask, ext_weights, ws, splits, T, patches, heads, R, lay, divp); \
+  } while (0)
+#define PARTIAL_LAUNCH1(KT, MT, PS)                                                                                  \
+  do {                                                                                                               \
+    if (nt) PARTIAL_LAUNCH2(KT, MT, PS, true); else PARTIAL_LAUNCH2(KT, MT, PS, false);                              \
   } while (0)
 #define PARTIAL_LAUNCH(KT, MT)                                                                                       \
   do {                                                                                                               \
@@ -545,6 +551,7 @@ extern "C" int dfd_decoder_attn_fwd(const float* q, const void* k, const void* v
   else { if (threads <= 512) PARTIAL_LAUNCH(bf16_t, 512); else PARTIAL_LAUNCH(bf16_t, 1024); }
 #undef PARTIAL_LAUNCH
 #undef PARTIAL_LAUNCH1
+#undef PARTIAL_LAUNCH2
   DFD_CHECK_LAUNCH("dfd_decoder_attn_fwd(partial)");
   if (combine_lds + combine_static > 64 * 1024)
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&decoder_attn_combine_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -611,15 +618,16 @@ extern "C" int dfd_linear_rows(const float* x, int64_t ldx, const float* W, cons
   if (B == 0) return DFD_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const dim3 grid((N + 3) / 4), block(256);
+  const bool nt = dfd_stream_on(DFD_STREAM_DECODER_WEIGHTS);
   switch (epilogue) {
     case DFD_EPI_BIAS:
-      hipLaunchKernelGGL((linear_rows_kernel<DFD_EPI_BIAS>), grid, block, 0, st, x, ldx, W, bias, y, ldy, B, N, K);
+      hipLaunchKernelGGL((nt ? linear_rows_kernel<DFD_EPI_BIAS, true> : linear_rows_kernel<DFD_EPI_BIAS, false>), grid, block, 0, st, x, ldx, W, bias, y, ldy, B, N, K);
       break;
     case DFD_EPI_BIAS_QUICKGELU:
-      hipLaunchKernelGGL((linear_rows_kernel<DFD_EPI_BIAS_QUICKGELU>), grid, block, 0, st, x, ldx, W, bias, y, ldy, B, N, K);
+      hipLaunchKernelGGL((nt ? linear_rows_kernel<DFD_EPI_BIAS_QUICKGELU, true> : linear_rows_kernel<DFD_EPI_BIAS_QUICKGELU, false>), grid, block, 0, st, x, ldx, W, bias, y, ldy, B, N, K);
       break;
     case DFD_EPI_BIAS_RESIDUAL:
-      hipLaunchKernelGGL((linear_rows_kernel<DFD_EPI_BIAS_RESIDUAL>), grid, block, 0, st, x, ldx, W, bias, y, ldy, B, N, K);
+      hipLaunchKernelGGL((nt ? linear_rows_kernel<DFD_EPI_BIAS_RESIDUAL, true> : linear_rows_kernel<DFD_EPI_BIAS_RESIDUAL, false>), grid, block, 0, st, x, ldx, W, bias, y, ldy, B, N, K);
       break;
     default:
       dfd_set_error("dfd_linear_rows: epilogue %d unsupported", epilogue);
@@ -655,9 +663,10 @@ extern "C" int dfd_linear_rows_t(const float* x, int64_t ldx, const float* Wt, c
   int rpw, ks;
   linear_t_plan(N, K, &rpw, &ks);
   float* part = static_cast<float*>(workspace);
+  const bool nt = dfd_stream_on(DFD_STREAM_DECODER_WEIGHTS);
   for (int b0 = 0; b0 < B; b0 += 16) {
     const int bb = B - b0 < 16 ? B - b0 : 16;
-    hipLaunchKernelGGL(linear_t_partial_kernel, dim3((N + LT_TILE - 1) / LT_TILE, ks), dim3(256), 0, st, x + (int64_t)b0 * ldx,
+    hipLaunchKernelGGL(nt ? linear_t_partial_kernel<true> : linear_t_partial_kernel<false>, dim3((N + LT_TILE - 1) / LT_TILE, ks), dim3(256), 0, st, x + (int64_t)b0 * ldx,
                        ldx, Wt, part, bb, N, K, rpw);
     DFD_CHECK_LAUNCH("dfd_linear_rows_t(partial)");
     const dim3 rg((bb * (N / 4) + 255) / 256), rb(256);

@@ -20,7 +20,7 @@ constexpr int HD = 64;
 __device__ __forceinline__ float sgn(float x) { return (float)(x > 0.f) - (float)(x < 0.f); }
 
 // grid (T, B).  part layout per (b, t): [heads][128] dq (softmax query | CoDA query), then [heads*64] dpos.
-template <typename T, typename G, int MAXT>
+template <typename T, typename G, int MAXT, bool NT>
 __global__ __launch_bounds__(MAXT) void decoder_attn_bwd_kernel(const float* __restrict__ q, const T* __restrict__ k,
                                                                 const T* __restrict__ v,
                                                                 const uint8_t* __restrict__ frame_mask,
@@ -89,8 +89,8 @@ __global__ __launch_bounds__(MAXT) void decoder_attn_bwd_kernel(const float* __r
 #pragma unroll
       for (int u = 0; u < UN; ++u) {
         const int j = min(j0 + u * R, patches - 1);
-        kq[u].load(kb + (int64_t)j * lay.row_stride);
-        vq[u].load(vb + (int64_t)j * lay.row_stride);
+        kq[u].template load<NT>(kb + (int64_t)j * lay.row_stride);
+        vq[u].template load<NT>(vb + (int64_t)j * lay.row_stride);
       }
       float ps[UN], pt[UN], pl[UN], pw[UN];
 #pragma unroll
@@ -267,6 +267,7 @@ __global__ void decoder_attn_bwd_reduce_kernel(const float* __restrict__ part, f
 }
 
 // dW[n, k] = Σ_b dy[b, n] x[b, k];  db[n] = Σ_b dy[b, n].  8 output rows per workgroup.
+template <bool NT>  // dW is written once and next read by the gradient pack (DFD_STREAM_DECODER_WEIGHTS)
 __global__ __launch_bounds__(256) void linear_bwd_weight_kernel(const float* __restrict__ dy, int64_t lddy,
                                                                 const float* __restrict__ x, int64_t ldx,
                                                                 float* __restrict__ dW, float* __restrict__ db, int B,
@@ -289,7 +290,7 @@ __global__ __launch_bounds__(256) void linear_bwd_weight_kernel(const float* __r
     }
 #pragma unroll
     for (int r = 0; r < 8; ++r)
-      if (n0 + r < N) *reinterpret_cast<f32x4*>(dW + (int64_t)(n0 + r) * K + kk) = acc[r];
+      if (n0 + r < N) stream_store16<NT>(dW + (int64_t)(n0 + r) * K + kk, acc[r]);
   }
   if (db != nullptr && threadIdx.x < 8 && n0 + threadIdx.x < N) {
     float s = 0.f;
@@ -457,14 +458,19 @@ extern "C" int dfd_decoder_attn_bwd(const float* q, const void* k, const void* v
   hipStream_t st = static_cast<hipStream_t>(stream);
   float* part = static_cast<float*>(workspace);
   const dim3 grid(T, B), block(threads);
-#define BWD_LAUNCH1(KT, GT, MT)                                                                                              \
+  const bool nt = dfd_stream_on(DFD_STREAM_DECODER_KV);
+#define BWD_LAUNCH2(KT, GT, MT, NT)                                                                                          \
   do {                                                                                                                      \
     if (lds > 64 * 1024)                                                                                                    \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&decoder_attn_bwd_kernel<KT, GT, MT>),                         \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&decoder_attn_bwd_kernel<KT, GT, MT, NT>),                     \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                      \
-    hipLaunchKernelGGL((decoder_attn_bwd_kernel<KT, GT, MT>), grid, block, lds, st, q, static_cast<const KT*>(k),              \
+    hipLaunchKernelGGL((decoder_attn_bwd_kernel<KT, GT, MT, NT>), grid, block, lds, st, q, static_cast<const KT*>(k),          \
                        static_cast<const KT*>(v), frame_mask, dmix, mix_softmax, stats, ext_weights, ext_dscores, part,      \
                        static_cast<GT*>(dk), static_cast<GT*>(dv), T, patches, heads, R, lay);                                    \
+  } while (0)
+#define BWD_LAUNCH1(KT, GT, MT)                                                                                              \
+  do {                                                                                                                      \
+    if (nt) BWD_LAUNCH2(KT, GT, MT, true); else BWD_LAUNCH2(KT, GT, MT, false);                                             \
   } while (0)
   // blocks of <= 512 threads (every even head count) get the 256-register budget: no spills with two rows in flight
 #define BWD_LAUNCH(KT, GT)                                                                                                  \
@@ -475,6 +481,7 @@ extern "C" int dfd_decoder_attn_bwd(const float* q, const void* k, const void* v
   if (kv_dtype == DFD_F32) { if (gb) BWD_LAUNCH(float, bf16_t); else BWD_LAUNCH(float, float); }
   else { if (gb) BWD_LAUNCH(bf16_t, bf16_t); else BWD_LAUNCH(bf16_t, float); }
 #undef BWD_LAUNCH1
+#undef BWD_LAUNCH2
 #undef BWD_LAUNCH
   DFD_CHECK_LAUNCH("dfd_decoder_attn_bwd");
   const int total = B * 2 * D + (dpos ? T * D : 0);
@@ -515,7 +522,7 @@ extern "C" int dfd_linear_rows_bwd_weight(const float* dy, int64_t lddy, const f
   DFD_REQUIRE(dy && x && dW, "dfd_linear_rows_bwd_weight: null pointer");
   DFD_REQUIRE(B > 0 && B <= 64 && N > 0 && K > 0 && K % 4 == 0 && ldx % 4 == 0, "dfd_linear_rows_bwd_weight: bad shape B=%d N=%d K=%d", B, N, K);
   DFD_REQUIRE(dfd_aligned16(x) && dfd_aligned16(dW), "dfd_linear_rows_bwd_weight: x and dW must be 16-byte aligned");
-  hipLaunchKernelGGL(linear_bwd_weight_kernel, dim3((N + 7) / 8), dim3(256), 0, static_cast<hipStream_t>(stream), dy, lddy, x,
+  hipLaunchKernelGGL(dfd_stream_on(DFD_STREAM_DECODER_WEIGHTS) ? linear_bwd_weight_kernel<true> : linear_bwd_weight_kernel<false>, dim3((N + 7) / 8), dim3(256), 0, static_cast<hipStream_t>(stream), dy, lddy, x,
                      ldx, dW, db, B, N, K);
   DFD_CHECK_LAUNCH("dfd_linear_rows_bwd_weight");
   return DFD_OK;

@@ -2,7 +2,7 @@
 // kernels: 8-element row pieces (one lane's share of a 64-wide head), the exchanges inside an 8-lane head group, tanh, a
 // key row's three sums and its CoDA weight.
 #pragma once
-#include "common.hpp"
+#include "stream_policy.hpp"
 
 namespace {
 
@@ -59,16 +59,17 @@ __device__ __forceinline__ float group8_reduce_scatter4(const float (&x)[4], int
   return (h1 ? z[1] : z[0]) + __shfl_xor(h1 ? z[0] : z[1], 1, 64);
 }
 
-// eight consecutive elements as loaded (bf16: 16 bytes, f32: 32 bytes), converted where they are used
+// eight consecutive elements as loaded (bf16: 16 bytes, f32: 32 bytes), converted where they are used; NT: the
+// non-temporal form, for the K / V rows a kernel reads once (DFD_STREAM_DECODER_KV)
 template <typename T> struct Raw8;
 template <> struct Raw8<float> {
   f32x4 a, b;
-  __device__ __forceinline__ void load(const float* p) { a = *reinterpret_cast<const f32x4*>(p); b = *reinterpret_cast<const f32x4*>(p + 4); }
+  template <bool NT = false> __device__ __forceinline__ void load(const float* p) { a = stream_load16<NT>(p); b = stream_load16<NT>(p + 4); }
   __device__ __forceinline__ float get(int e) const { return e < 4 ? a[e] : b[e - 4]; }
 };
 template <> struct Raw8<bf16_t> {
   bf16x8 a;
-  __device__ __forceinline__ void load(const bf16_t* p) { a = *reinterpret_cast<const bf16x8*>(p); }
+  template <bool NT = false> __device__ __forceinline__ void load(const bf16_t* p) { a = __builtin_bit_cast(bf16x8, stream_load16<NT>(p)); }
   __device__ __forceinline__ float get(int e) const { return (float)a[e]; }
 };
 

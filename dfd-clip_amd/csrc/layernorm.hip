@@ -7,7 +7,7 @@
 //   (clip/model.py:157-163).
 // dfd_patchify: frames [N,3,R,R] f32 -> patch rows [N*P, kpad] so that the patch conv
 //   (clip/model.py:264, :277) is a plain A·Wᵀ GEMM with W = conv1.weight.view(D, 3*p*p).
-#include "common.hpp"
+#include "stream_policy.hpp"
 #include "../../include/dfdclip_ext.h"
 
 // e4m3 output (the A operand of an fp8 GEMM, dfd_gemm_fp8): stored value = e4m3(y * inv_scale), saturated at +-448
@@ -33,10 +33,12 @@ __device__ __forceinline__ void store_row4(OutT* p, f32x4 o, float inv_scale) {
   }
 }
 
+// NT (all three row kernels, DFD_STREAM_ENCODER_ROWS): the f32 residual stream x and the pending deltas are read once and
+// x is written once, with non-temporal loads and stores; y, which the next GEMM reads, always takes the plain store.
 // DUAL (all three row kernels): the row is also written as e4m3 to y8 (row stride ldy8) from the registers that hold the
 // normalised f32 values — OutT is bf16 then, and inv_scale belongs to y8.  A "kv-bf16" layer of the fp8 encoder reads its
 // LayerNorm output in both formats (encoder.py); a second LayerNorm call would read the f32 residual stream once more.
-template <typename OutT, int SLABS, bool DUAL = false>
+template <typename OutT, int SLABS, bool DUAL = false, bool NT = false>
 __global__ __launch_bounds__(256) void layernorm_rows_kernel(const float* __restrict__ x, int64_t ldx,
                                                              const float* __restrict__ gamma,
                                                              const float* __restrict__ beta, OutT* __restrict__ y,
@@ -52,7 +54,7 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const float* __rest
   for (int i = 0; i < SLABS; ++i) {
     const int c = (i * 64 + lane) * 4;
     if (c < cols) {
-      v[i] = *reinterpret_cast<const f32x4*>(xr + c);
+      v[i] = stream_load16<NT>(xr + c);
       s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
     } else {
       v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -93,10 +95,12 @@ static int launch_ln(const float* x, int64_t ldx, const float* g, const float* b
                      int cols, float eps, float inv_scale, hipStream_t st) {
   const int slabs = (cols + 255) / 256;
   const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+  const bool nt = dfd_stream_on(DFD_STREAM_ENCODER_ROWS);
   OutT* yo = static_cast<OutT*>(y);
 #define LN_CASE(S)                                                                                     \
   case S:                                                                                              \
-    hipLaunchKernelGGL((layernorm_rows_kernel<OutT, S>), grid, block, 0, st, x, ldx, g, b, yo, ldy, rows, cols, eps, inv_scale); \
+    hipLaunchKernelGGL((nt ? layernorm_rows_kernel<OutT, S, false, true> : layernorm_rows_kernel<OutT, S>), grid, block, 0, st, x, ldx, g, b, yo, ldy, rows, cols, eps, inv_scale, \
+                       static_cast<fp8_t*>(nullptr), (int64_t)0); \
     break;
   switch (slabs) {
     LN_CASE(1) LN_CASE(2) LN_CASE(3) LN_CASE(4) LN_CASE(5) LN_CASE(6) LN_CASE(7) LN_CASE(8)
@@ -113,7 +117,7 @@ static int launch_ln(const float* x, int64_t ldx, const float* g, const float* b
 // Two LayerNorms back to back over the same rows in one pass: x <- LN_a(x) (f32, in place), y = LN_b(x).  The
 // encoder's ln_pre followed by the first block's ln_1 (clip/model.py:292, :221): the row stays in registers between
 // the two, so x is read once instead of twice.  Same arithmetic, in the same order, as two dfd_layernorm calls.
-template <typename OutT, int SLABS, bool DUAL = false>
+template <typename OutT, int SLABS, bool DUAL = false, bool NT = false>
 __global__ __launch_bounds__(256) void layernorm2_rows_kernel(float* __restrict__ x, int64_t ldx, const float* __restrict__ ga,
                                                               const float* __restrict__ ba, const float* __restrict__ gb,
                                                               const float* __restrict__ bb, OutT* __restrict__ y, int64_t ldy,
@@ -131,7 +135,7 @@ __global__ __launch_bounds__(256) void layernorm2_rows_kernel(float* __restrict_
     for (int i = 0; i < SLABS; ++i) {
       const int c = (i * 64 + lane) * 4;
       if (c < cols) {
-        if (pass == 0) v[i] = *reinterpret_cast<const f32x4*>(xr + c);
+        if (pass == 0) v[i] = stream_load16<NT>(xr + c);
         s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
       } else {
         v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -163,7 +167,7 @@ __global__ __launch_bounds__(256) void layernorm2_rows_kernel(float* __restrict_
 #pragma unroll
         for (int j = 0; j < 4; ++j) o[j] = (v[i][j] - mean) * rstd * g[j] + b[j];
         if (pass == 0) {
-          *reinterpret_cast<f32x4*>(xr + c) = o;
+          stream_store16<NT>(xr + c, o);
           v[i] = o;
         } else {
           store_row4(y + row * ldy + c, o, inv_scale);
@@ -179,10 +183,12 @@ static int launch_ln2(float* x, int64_t ldx, const float* ga, const float* ba, c
                       int64_t rows, int cols, float eps, float inv_scale, hipStream_t st) {
   const int slabs = (cols + 255) / 256;
   const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+  const bool nt = dfd_stream_on(DFD_STREAM_ENCODER_ROWS);
   OutT* yo = static_cast<OutT*>(y);
 #define LN2_CASE(S)                                                                                    \
   case S:                                                                                              \
-    hipLaunchKernelGGL((layernorm2_rows_kernel<OutT, S>), grid, block, 0, st, x, ldx, ga, ba, gb, bb, yo, ldy, rows, cols, eps, inv_scale); \
+    hipLaunchKernelGGL((nt ? layernorm2_rows_kernel<OutT, S, false, true> : layernorm2_rows_kernel<OutT, S>), grid, block, 0, st, x, ldx, ga, ba, gb, bb, yo, ldy, rows, cols, eps, inv_scale, \
+                       static_cast<fp8_t*>(nullptr), (int64_t)0); \
     break;
   switch (slabs) {
     LN2_CASE(1) LN2_CASE(2) LN2_CASE(3) LN2_CASE(4) LN2_CASE(5) LN2_CASE(6) LN2_CASE(7) LN2_CASE(8)
@@ -234,7 +240,7 @@ extern "C" int dfd_layernorm(const float* x, int64_t ldx, const float* gamma, co
 // per wave of tiles with every CU in its epilogue at once), and folds the add into the LayerNorm
 // that follows — exactly torch autocast's dataflow (Linear output in bf16, added to the fp32 stream).
 // Bytes per row: cols * (4 + sizeof(delta) + 4 + sizeof(y)).
-template <typename DeltaT, typename OutT, int SLABS, bool DUAL = false>
+template <typename DeltaT, typename OutT, int SLABS, bool DUAL = false, bool NT = false>
 __global__ __launch_bounds__(256) void add_layernorm_rows_kernel(float* __restrict__ x, int64_t ldx,
                                                                  const DeltaT* __restrict__ delta, int64_t ldd,
                                                                  const DeltaT* __restrict__ delta2, int store_x,
@@ -253,21 +259,21 @@ __global__ __launch_bounds__(256) void add_layernorm_rows_kernel(float* __restri
   for (int i = 0; i < SLABS; ++i) {
     const int c = (i * 64 + lane) * 4;
     if (c < cols) {
-      v[i] = *reinterpret_cast<const f32x4*>(xr + c);
+      v[i] = stream_load16<NT>(xr + c);
       auto add = [&](const DeltaT* p) {
         if constexpr (sizeof(DeltaT) == 4) {
-          const f32x4 d = *reinterpret_cast<const f32x4*>(p + c);
+          const f32x4 d = stream_load16<NT>(p + c);
 #pragma unroll
           for (int j = 0; j < 4; ++j) v[i][j] += d[j];
         } else {
-          const bf16x4 d = *reinterpret_cast<const bf16x4*>(p + c);
+          const bf16x4 d = __builtin_bit_cast(bf16x4, stream_load8<NT>(p + c));
 #pragma unroll
           for (int j = 0; j < 4; ++j) v[i][j] += (float)d[j];
         }
       };
       add(dr);                                             // (x + delta) + delta2: the order of the two
       if (delta2 != nullptr) add(delta2 + row * ldd);      // separate adds it replaces
-      if (store_x) *reinterpret_cast<f32x4*>(xr + c) = v[i];
+      if (store_x) stream_store16<NT>(xr + c, v[i]);
       s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
     } else {
       v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -308,13 +314,14 @@ static int launch_add_ln(float* x, int64_t ldx, const void* delta, int64_t ldd, 
                          const float* b, void* y, int64_t ldy, int64_t rows, int cols, float eps, float inv_scale, hipStream_t st) {
   const int slabs = (cols + 255) / 256;
   const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+  const bool nt = dfd_stream_on(DFD_STREAM_ENCODER_ROWS);
   const DeltaT* dd = static_cast<const DeltaT*>(delta);
   const DeltaT* dd2 = static_cast<const DeltaT*>(delta2);
   OutT* yo = static_cast<OutT*>(y);
 #define ALN_CASE(S)                                                                                                   \
   case S:                                                                                                             \
-    hipLaunchKernelGGL((add_layernorm_rows_kernel<DeltaT, OutT, S>), grid, block, 0, st, x, ldx, dd, ldd, dd2, store_x, g, b,  \
-                       yo, ldy, rows, cols, eps, inv_scale);                                                          \
+    hipLaunchKernelGGL((nt ? add_layernorm_rows_kernel<DeltaT, OutT, S, false, true> : add_layernorm_rows_kernel<DeltaT, OutT, S>), grid, block, 0, st, x, ldx, dd, ldd, dd2, store_x, g, b,  \
+                       yo, ldy, rows, cols, eps, inv_scale, static_cast<fp8_t*>(nullptr), (int64_t)0);                                                          \
     break;
   switch (slabs) {
     ALN_CASE(1) ALN_CASE(2) ALN_CASE(3) ALN_CASE(4) ALN_CASE(5) ALN_CASE(6) ALN_CASE(7) ALN_CASE(8)
@@ -390,10 +397,11 @@ extern "C" int dfd_layernorm_dual(const float* x, int64_t ldx, const float* gamm
   if (rows == 0) return DFD_OK;
   const int slabs = (cols + 255) / 256;
   const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+  const bool nt = dfd_stream_on(DFD_STREAM_ENCODER_ROWS);
   hipStream_t st = static_cast<hipStream_t>(stream);
 #define LND_CASE(S)                                                                                                          \
   case S:                                                                                                                    \
-    hipLaunchKernelGGL((layernorm_rows_kernel<bf16_t, S, true>), grid, block, 0, st, x, ldx, gamma, beta, static_cast<bf16_t*>(y16), \
+    hipLaunchKernelGGL((nt ? layernorm_rows_kernel<bf16_t, S, true, true> : layernorm_rows_kernel<bf16_t, S, true>), grid, block, 0, st, x, ldx, gamma, beta, static_cast<bf16_t*>(y16), \
                        ldy16, rows, cols, eps, y8_inv_scale, static_cast<fp8_t*>(y8), ldy8);                                 \
     break;
   switch (slabs) {
@@ -418,10 +426,11 @@ extern "C" int dfd_layernorm2_dual(float* x, int64_t ldx, const float* gamma_a, 
   if (rows == 0) return DFD_OK;
   const int slabs = (cols + 255) / 256;
   const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+  const bool nt = dfd_stream_on(DFD_STREAM_ENCODER_ROWS);
   hipStream_t st = static_cast<hipStream_t>(stream);
 #define LN2D_CASE(S)                                                                                                         \
   case S:                                                                                                                    \
-    hipLaunchKernelGGL((layernorm2_rows_kernel<bf16_t, S, true>), grid, block, 0, st, x, ldx, gamma_a, beta_a, gamma_b, beta_b, \
+    hipLaunchKernelGGL((nt ? layernorm2_rows_kernel<bf16_t, S, true, true> : layernorm2_rows_kernel<bf16_t, S, true>), grid, block, 0, st, x, ldx, gamma_a, beta_a, gamma_b, beta_b, \
                        static_cast<bf16_t*>(y16), ldy16, rows, cols, eps, y8_inv_scale, static_cast<fp8_t*>(y8), ldy8);      \
     break;
   switch (slabs) {
@@ -438,11 +447,12 @@ static int launch_add_ln_dual(float* x, int64_t ldx, const void* delta, int64_t 
                               float inv_scale, hipStream_t st) {
   const int slabs = (cols + 255) / 256;
   const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+  const bool nt = dfd_stream_on(DFD_STREAM_ENCODER_ROWS);
   const DeltaT* dd = static_cast<const DeltaT*>(delta);
   const DeltaT* dd2 = static_cast<const DeltaT*>(delta2);
 #define ALND_CASE(S)                                                                                                         \
   case S:                                                                                                                    \
-    hipLaunchKernelGGL((add_layernorm_rows_kernel<DeltaT, bf16_t, S, true>), grid, block, 0, st, x, ldx, dd, ldd, dd2, store_x, g, b, \
+    hipLaunchKernelGGL((nt ? add_layernorm_rows_kernel<DeltaT, bf16_t, S, true, true> : add_layernorm_rows_kernel<DeltaT, bf16_t, S, true>), grid, block, 0, st, x, ldx, dd, ldd, dd2, store_x, g, b, \
                        static_cast<bf16_t*>(y16), ldy16, rows, cols, eps, inv_scale, static_cast<fp8_t*>(y8), ldy8);         \
     break;
   switch (slabs) {
@@ -481,6 +491,7 @@ extern "C" int dfd_add_layernorm_dual(float* x, int64_t ldx, const void* delta, 
 // Its input is 3*p image rows read as whole rows (16 bytes per lane, fully coalesced); its output, the grid_w patch
 // rows of that strip, is ONE contiguous run (grid_w * 3*p*p bf16).  The transpose goes through LDS: a patch's
 // 3*p*p bf16 at stride 3*p*p*2 + 32 bytes (the 8-byte writes of neighbouring patches land 8 banks apart).
+template <bool NT>  // NT (DFD_STREAM_ENCODER_ROWS): the frames are read once
 __global__ __launch_bounds__(256) void patchify_strip_kernel(const float* __restrict__ frames, bf16_t* __restrict__ out, int res,
                                                              int patch) {
   extern __shared__ __attribute__((aligned(16))) unsigned char strip[];
@@ -493,7 +504,7 @@ __global__ __launch_bounds__(256) void patchify_strip_kernel(const float* __rest
   for (int idx = threadIdx.x; idx < nq; idx += 256) {
     const int rw = idx / qrow, xq = idx - rw * qrow;  // rw = c*patch + i
     const int c = rw / patch, i = rw - c * patch;
-    const f32x4 v = *reinterpret_cast<const f32x4*>(frames + (((int64_t)n * 3 + c) * res + (gy * patch + i)) * res + xq * 4);
+    const f32x4 v = stream_load16<NT>(frames + (((int64_t)n * 3 + c) * res + (gy * patch + i)) * res + xq * 4);
     const int x = xq * 4, gx = x / patch, j = x - gx * patch;
     bf16x4 o;
 #pragma unroll
@@ -566,7 +577,7 @@ extern "C" int dfd_patchify(const float* frames, void* patches, int out_dtype, i
   const size_t strip_lds = (size_t)(res / patch) * (kk * 2 + 32);
   if (out_dtype == DFD_BF16 && patch % 4 == 0 && kpad == kk && strip_lds <= 64 * 1024 && dfd_aligned16(frames) &&
       (int64_t)n_frames * (res / patch) < (int64_t)0x7fffffff) {
-    hipLaunchKernelGGL(patchify_strip_kernel, dim3((unsigned)(n_frames * (res / patch))), dim3(256), strip_lds, st, frames,
+    hipLaunchKernelGGL(dfd_stream_on(DFD_STREAM_ENCODER_ROWS) ? patchify_strip_kernel<true> : patchify_strip_kernel<false>, dim3((unsigned)(n_frames * (res / patch))), dim3(256), strip_lds, st, frames,
                        static_cast<bf16_t*>(patches), res, patch);
     DFD_CHECK_LAUNCH("dfd_patchify(strip)");
     return DFD_OK;

@@ -15,7 +15,7 @@
 #include <cmath>
 #include <cstddef>
 
-#include "common.hpp"
+#include "stream_policy.hpp"
 
 namespace {
 
@@ -31,7 +31,8 @@ struct SgdEntry {      // mirrors dfd_sgd_param of the C ABI
 
 // The traversal both optimizers share: find this workgroup's entry, then hand `update(entry index, entry, element)`
 // (which returns the new parameter value) every element of its block or tile.
-template <class Update>
+// NT (DFD_STREAM_OPTIMIZER): every byte here is touched once per step, and the mirror's next reader is a step away.
+template <bool NT, class Update>
 __device__ __forceinline__ void step_entries(const SgdEntry* __restrict__ table, int n, float (*tile)[33], Update update) {
   const int64_t b = blockIdx.x;
   int lo = 0, hi = n - 1;  // last entry whose first_block <= b
@@ -63,20 +64,21 @@ __device__ __forceinline__ void step_entries(const SgdEntry* __restrict__ table,
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int c = tc * 32 + ty + 8 * k, r = tr * 32 + tx;  // mirror row = parameter column
-    if (r < e.rows && c < e.cols) e.mirror[(int64_t)c * e.rows + r] = tile[tx][ty + 8 * k];
+    if (r < e.rows && c < e.cols) stream_store4<NT>(e.mirror + (int64_t)c * e.rows + r, tile[tx][ty + 8 * k]);
   }
 }
 
+template <bool NT>
 __global__ __launch_bounds__(256) void sgd_step_kernel(const SgdEntry* __restrict__ table, int n, float lr, float momentum, float wd, int first) {
   __shared__ float tile[32][33];
-  step_entries(table, n, tile, [&](int, const SgdEntry& e, int64_t i) {
-    const float p = e.p[i];
-    const float g = __builtin_fmaf(wd, p, e.g[i]);
+  step_entries<NT>(table, n, tile, [&](int, const SgdEntry& e, int64_t i) {
+    const float p = stream_load4<NT>(e.p + i);
+    const float g = __builtin_fmaf(wd, p, stream_load4<NT>(e.g + i));
     float m = g;
-    if (!first) m = momentum * e.buf[i] + g;
-    e.buf[i] = m;
+    if (!first) m = momentum * stream_load4<NT>(e.buf + i) + g;
+    stream_store4<NT>(e.buf + i, m);
     const float np = __builtin_fmaf(-lr, m, p);
-    e.p[i] = np;
+    stream_store4<NT>(e.p + i, np);
     return np;
   });
 }
@@ -96,23 +98,24 @@ struct AdamwArgs {
   int decay_on;
 };
 
+template <bool NT>
 __global__ __launch_bounds__(256) void adamw_step_kernel(const SgdEntry* __restrict__ table, int n, float* const* __restrict__ vs, AdamwArgs a) {
   __shared__ float tile[32][33];
-  step_entries(table, n, tile, [&](int idx, const SgdEntry& e, int64_t i) {
+  step_entries<NT>(table, n, tile, [&](int idx, const SgdEntry& e, int64_t i) {
     float* __restrict__ vv = vs[idx];
-    float p = e.p[i];
-    const float g = e.g[i];
-    float m = e.buf[i], v = vv[i];
+    float p = stream_load4<NT>(e.p + i);
+    const float g = stream_load4<NT>(e.g + i);
+    float m = stream_load4<NT>(e.buf + i), v = stream_load4<NT>(vv + i);
     if (a.decay_on) p *= a.decay;
     const float d = g - m;
     m = a.w1 < 0.5f ? __builtin_fmaf(a.w1, d, m) : __builtin_fmaf(-d, 1.0f - a.w1, g);
     v *= a.beta2;
     v = __builtin_fmaf(a.w2, g * g, v);
-    e.buf[i] = m;
-    vv[i] = v;
+    stream_store4<NT>(e.buf + i, m);
+    stream_store4<NT>(vv + i, v);
     const float den = __builtin_sqrtf(v) / a.bc2_sqrt + a.eps;
     p = __builtin_fmaf(a.step_size, m / den, p);
-    e.p[i] = p;
+    stream_store4<NT>(e.p + i, p);
     return p;
   });
 }
@@ -136,8 +139,9 @@ extern "C" int dfd_sgd_step(const dfd_sgd_param* table_dev, int n, int64_t total
   DFD_REQUIRE(table_dev != nullptr && n > 0, "dfd_sgd_step: empty table");
   DFD_REQUIRE(total_blocks > 0 && total_blocks < ((int64_t)1 << 31), "dfd_sgd_step: total_blocks = %lld", (long long)total_blocks);
   const auto* table = reinterpret_cast<const SgdEntry*>(table_dev);
+  const bool nt = dfd_stream_on(DFD_STREAM_OPTIMIZER);
   if (extra == nullptr || extra->kind == DFD_OPTIM_SGD) {
-    hipLaunchKernelGGL(sgd_step_kernel, dim3((unsigned)total_blocks), dim3(256), 0, static_cast<hipStream_t>(stream), table, n, lr,
+    hipLaunchKernelGGL(nt ? sgd_step_kernel<true> : sgd_step_kernel<false>, dim3((unsigned)total_blocks), dim3(256), 0, static_cast<hipStream_t>(stream), table, n, lr,
                        momentum, weight_decay, first_step);
     DFD_CHECK_LAUNCH("dfd_sgd_step");
     return DFD_OK;
@@ -159,7 +163,7 @@ extern "C" int dfd_sgd_step(const dfd_sgd_param* table_dev, int n, int64_t total
   a.bc2_sqrt = (float)std::pow(1.0 - std::pow(b2, t), 0.5);
   a.eps = (float)extra->eps;
   a.step_size = (float)((lrd / (1.0 - std::pow(b1, t))) * -1.0);
-  hipLaunchKernelGGL(adamw_step_kernel, dim3((unsigned)total_blocks), dim3(256), 0, static_cast<hipStream_t>(stream), table, n,
+  hipLaunchKernelGGL(nt ? adamw_step_kernel<true> : adamw_step_kernel<false>, dim3((unsigned)total_blocks), dim3(256), 0, static_cast<hipStream_t>(stream), table, n,
                      extra->exp_avg_sq, a);
   DFD_CHECK_LAUNCH("dfd_sgd_step");
   return DFD_OK;

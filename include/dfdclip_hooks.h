@@ -31,6 +31,23 @@ int dfd_gemm_pair_plan(int64_t M, int D, int H);
  * DFD_GEMM_C_BLOCKED or DFD_GEMM_A_BLOCKED in force; not the calls variant 1 turned row-major).  For tests. */
 int64_t dfd_gemm_pair_launches(void);
 
+/* The cache policy of the kernels that touch every byte once.  One bit per family; a set bit makes that family's loads
+ * and stores of its read-once (write-once) stream non-temporal, so that they do not evict what the persistent GEMMs of
+ * another stream keep in L2.  Results are bit-identical either way (tests/test_hip_stream_policy.py).  Process-wide
+ * (the backward pass launches from another thread than the forward); read at launch, so a captured graph keeps what was
+ * set at capture.  `set` returns the previous mask; DFD_STREAM_DEFAULT is what the library starts with. */
+enum {
+  DFD_STREAM_DECODER_KV = 1,      /* K / V loads of dfd_decoder_attn_fwd and dfd_decoder_attn_bwd */
+  DFD_STREAM_DECODER_WEIGHTS = 2, /* weight loads of dfd_linear_rows / dfd_linear_rows_t, dW stores of dfd_linear_rows_bwd_weight */
+  DFD_STREAM_OPTIMIZER = 4,       /* dfd_sgd_step: gradient, state and parameter loads; state, parameter and mirror stores */
+  DFD_STREAM_ENCODER_ROWS = 8,    /* the LayerNorm family's f32 x / delta loads and f32 x store; dfd_patchify's frame loads */
+  DFD_STREAM_ALL = 15
+};
+/* DECODER_KV | ENCODER_ROWS: the families that passed the rule of DESIGN.md section 7.1b */
+#define DFD_STREAM_DEFAULT 9
+unsigned dfd_stream_policy_set(unsigned mask);
+unsigned dfd_stream_policy_get(void);
+
 #ifdef __cplusplus
 }
 #endif
