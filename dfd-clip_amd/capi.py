@@ -170,6 +170,23 @@ AUGMENT_SIGNATURES = {
     "dfd_augment_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
 }
 
+class AlignFrame(Structure):
+    """dfd_align_frame_t (include/dfdclip_align.h): one frame's inverse map, crop origin, window origin and border."""
+    _fields_ = [("q", c_int64 * 6), ("x0", c_int32), ("y0", c_int32), ("win_x", c_int32), ("win_y", c_int32), ("border", c_int32),
+                ("flags", c_uint32)]
+
+
+ALIGN_HWC, ALIGN_CHW = 0, 1
+ALIGN_SWAP_RB = 1
+ALIGN_FRAME_INVALID = 1
+ALIGN_FRAME_BYTES = ctypes.sizeof(AlignFrame)  # the header documents it as DFD_ALIGN_FRAME_BYTES
+
+# face alignment beside the ABI, in a header of its own (include/dfdclip_align.h)
+ALIGN_SIGNATURES = {
+    "dfd_align_crop_u8": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_uint32,
+                                  c_void_p]),
+}
+
 # test / measurement hooks outside the ABI header (include/dfdclip_hooks.h)
 HOOK_SIGNATURES = {
     "dfd_attention_set_variant": (c_int, [c_int]),
@@ -198,7 +215,8 @@ def load_library(path=None):
     if not os.path.exists(path):
         raise DfdError(f"{path} not found: the HIP kernel library is not built and there is no fallback path")
     lib = ctypes.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **EXPLAIN_SIGNATURES, **AUGMENT_SIGNATURES, **HOOK_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **EXPLAIN_SIGNATURES, **AUGMENT_SIGNATURES, **ALIGN_SIGNATURES,
+                               **HOOK_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError:
@@ -360,6 +378,24 @@ def augment_u8(frames, out, sets, set_of_frame):
     assert set_of_frame.dtype == torch.int32 and set_of_frame.is_contiguous() and set_of_frame.numel() == n
     _check(load_library().dfd_augment_u8(_ptr(frames), _ptr(out), n, h, w, _ptr(sets), sets.shape[0], _ptr(set_of_frame), _stream()),
            "dfd_augment_u8")
+    return out
+
+
+def align_crop_u8(src, out, records, layout, row_stride, frame_stride, win_h, win_w, swap_rb=False):
+    """out [n,3,oh,ow] u8 = the face-aligned crops of the n source windows behind `src` (include/dfdclip_align.h): `src` any u8
+    device tensor whose memory from its first element on holds the frames at the given byte strides (`layout` ALIGN_HWC:
+    [win_h, win_w, 3] interleaved, ALIGN_CHW: [3, win_h, win_w] planar), `records` u8 [n, ALIGN_FRAME_BYTES] =
+    dfd_align_frame_t.  The device-side `affine_transform` + `cut_patch` of reference `pipeline.py:114-182`."""
+    _dev(src, out, records)
+    assert src.dtype == torch.uint8 and out.dtype == torch.uint8 and out.dim() == 4 and out.shape[1] == 3 and out.is_contiguous()
+    n, _, oh, ow = out.shape
+    assert records.dtype == torch.uint8 and records.is_contiguous() and tuple(records.shape) == (n, ALIGN_FRAME_BYTES)
+    if n > 0 and win_h > 0 and win_w > 0:  # the memory behind `src` must hold what the strides describe
+        span = (n - 1) * frame_stride + (win_h * (1 if layout == ALIGN_HWC else 3) - 1) * row_stride + win_w * (3 if layout == ALIGN_HWC else 1)
+        have = src.untyped_storage().nbytes() - src.storage_offset()
+        assert span <= have, f"the strides describe {span} bytes, the tensor's memory holds {have} from its first element on"
+    _check(load_library().dfd_align_crop_u8(_ptr(src), int(layout), int(row_stride), int(frame_stride), int(win_h), int(win_w), _ptr(out),
+                                            n, oh, ow, _ptr(records), ALIGN_SWAP_RB if swap_rb else 0, _stream()), "dfd_align_crop_u8")
     return out
 
 

@@ -24,6 +24,9 @@ code, so that a reference user finds the same step semantics on top of `Detector
   infer_videos    `inference.py:105-162`: per video, chunks of `batch_size` clips -> predict -> softmax ->
                   clip- or video-level (mean over clips) probabilities -> gather -> accuracy / AUROC with
                   the dummy [0, 1] pair the reference appends before computing.
+  infer_raw_video `pipeline.py:114-182` + `:328-351`: decoded frames + landmarks -> face-aligned crops on the device
+                  (`align.FaceAligner`) -> clips of num_frames, ragged tail dropped -> predict in chunks -> softmax ->
+                  mean over clips -> probability of class 1.
 """
 import copy
 
@@ -248,6 +251,35 @@ def infer_videos(model, videos, batch_size=30, modality="video", task_index=0, d
     pred2 = torch.cat([probs.argmax(dim=-1), torch.tensor([0, 1])])
     return dict(accuracy=round((pred2 == lab2).float().mean().item(), 3), roc_auc=round(binary_auroc(lab2, sc2), 3),
                 labels=labels, probs=probs)
+
+
+@torch.no_grad()
+def infer_raw_video(model, frames, landmarks, aligner, batch_size=16, task_index=0, layout="hwc", swap_rb=False, with_logits=False):
+    """One decoded video to a verdict, as `pipeline.get_result` does after its file handling (`pipeline.py:328-351`), with
+    the face alignment it reads from a pre-cropped file done here on the device (`align.FaceAligner`).
+
+    frames: uint8 device frames [F,H,W,3] (`layout="hwc"`) or [F,3,H,W]; landmarks [F,68,2]; `aligner.plan` /
+    `aligner.apply` turn them into [F,3,crop,crop] crops.  The frames are cut into clips of `model.num_frames`
+    consecutive frames, a ragged last clip is dropped (`pipeline.py:334-336`), `predict` runs on uint8 clips in chunks of
+    `batch_size` with `plan.valid` (frames with a face) as the mask, and the softmax is averaged over clips.
+    Returns (probability of class 1, per-clip probabilities [clips, classes]) on the host; `with_logits` appends the
+    per-clip logits."""
+    model.eval()
+    plan = aligner.plan(landmarks)
+    crops = aligner.apply(frames, plan, layout=layout, swap_rb=swap_rb)
+    T = int(model.num_frames)
+    n = crops.shape[0] // T
+    if n == 0:
+        raise ValueError(f"{crops.shape[0]} frames do not fill one clip of {T}")
+    clips = crops[:n * T].view(n, T, *crops.shape[1:])
+    mask = torch.from_numpy(plan.valid[:n * T].copy()).view(n, T).to(crops.device)
+    logits = []
+    for i in range(0, n, batch_size):
+        logits.append(model.predict(clips[i:i + batch_size], mask[i:i + batch_size])[0][task_index].detach().to("cpu"))
+    logits = torch.cat(logits)
+    p = logits.softmax(dim=-1)
+    res = (p.mean(dim=0)[1], p)
+    return res + (logits,) if with_logits else res
 
 
 # ---- patch saliency guides (train_mode.patch_mask.type: guide) -----------------------------------------------------
