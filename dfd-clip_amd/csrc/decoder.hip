@@ -19,9 +19,6 @@
 
 namespace {
 
-constexpr int HD = 64;
-constexpr int PART = 2 + 2 * HD;  // floats per (clip, split, head): m, l, acc_s[64], acc_c[64]
-
 template <typename T, int MAXT, bool POS, bool NT>
 __global__ __launch_bounds__(MAXT, (MAXT <= 512 ? (POS ? 2 : 3) : 4)) void decoder_attn_partial_kernel(const float* __restrict__ q, const T* __restrict__ k,
                                                                     const T* __restrict__ v,
@@ -31,87 +28,40 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 512 ? (POS ? 2 : 3) : 4)) void decod
                                                                     int patches, int heads, int R, KvLayout lay,
                                                                     FastDiv div_patches) {
   extern __shared__ float red[];  // [R][tpr][18], then (POS) the positional embedding of this block's frames
-  const int tpr = heads * 8;
+  const HeadLanes ln(heads);
+  const int tpr = ln.tpr, rs = ln.rs, tr = ln.tr, hd = ln.hd, sub = ln.sub;
   const int b = blockIdx.y, split = blockIdx.x;
-  const int rs = threadIdx.x / tpr, tr = threadIdx.x % tpr;
-  const int hd = tr >> 3, sub = tr & 7;
   const int S = T_frames * patches;
   const int D = heads * HD;
   const int per = (S + splits - 1) / splits;
   const int s_begin = split * per;
   const int s_end = min(S, s_begin + per);
-  // POS: the rows of this block lie in frames f0 .. f1 of the clip; their positional embeddings are staged in LDS
-  // once (held in registers they cost the kernel half its occupancy)
-  [[maybe_unused]] float* const posl = red + (size_t)blockDim.x * 18;
-  [[maybe_unused]] const int f0 = (int)div_patches.div((uint32_t)min(s_begin, S - 1));
-  if constexpr (POS) {
-    const int f1 = (int)div_patches.div((uint32_t)(max(s_end, s_begin + 1) - 1 < S ? max(s_end, s_begin + 1) - 1 : S - 1));
-    const int n4 = (f1 - f0 + 1) * (D >> 2);
-    for (int i = threadIdx.x; i < n4; i += blockDim.x)
-      reinterpret_cast<f32x4*>(posl)[i] = reinterpret_cast<const f32x4*>(lay.pos + (int64_t)f0 * D)[i];
-    __syncthreads();
-  }
+  float* const posl = red + (size_t)blockDim.x * 18;
+  const int f0 = stage_pos<POS>(posl, lay.pos, s_begin, s_end, S, D, div_patches);
 
   float qs[8], qc[8];
-  {
-    const float* qp = q + ((int64_t)b * heads + hd) * (2 * HD) + sub * 8;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      qs[e] = qp[e] * 0.125f;
-      qc[e] = qp[HD + e];
-    }
-  }
+  load_query(q, b, heads, ln, 0.125f, qs, qc);
   float mx = -INFINITY, l = 0.f, as[8], ac[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) { as[e] = 0.f; ac[e] = 0.f; }
 
-  // row s of clip b = patch (s % patches) of frame b*T + s / patches (KvLayout: dense export or the qkv activation in place)
-  const T* kb = k + (int64_t)b * T_frames * lay.frame_stride + hd * HD + sub * 8;
-  const T* vb = v + (int64_t)b * T_frames * lay.frame_stride + hd * HD + sub * 8;
-  [[maybe_unused]] const float* const pb = posl + hd * HD + sub * 8;
-  const uint8_t* mb = frame_mask + (int64_t)b * T_frames;
-  const int lane_base = (threadIdx.x & 63) & ~7;
-  // Eight rows per trip, one per lane of the 8-lane head group, all sixteen loads issued before the first use (the
-  // loop is a latency chain otherwise).  Every lane forms its 8-channel share of the three dot products of all eight
-  // rows; a reduce-scatter over the group leaves lane j with the totals of row j, so the row's transcendentals
-  // (exp, tanh, sigmoid: the VALU bulk of this kernel) run ONCE per row instead of once per lane; the row weights
-  // then travel back to the group for the V accumulation.  The softmax is rescaled once per trip.
-  constexpr int UN = 8;
+  const T* kb = ln.channels(k + (int64_t)b * T_frames * lay.frame_stride);
+  const T* vb = ln.channels(v + (int64_t)b * T_frames * lay.frame_stride);
+  const KeySpan sp{s_end, S, D, f0, patches, R, lay, div_patches, frame_mask + (int64_t)b * T_frames, ln.channels(posl)};
+  // The front (key_trip) leaves this lane with the sums of its own row of the trip; the row weights then travel back to
+  // the group for the V accumulation.  The softmax is rescaled once per trip.
   float l_own = 0.f;  // softmax weights of the rows this lane finished; summed over the group at the end
   for (int s0 = s_begin + rs; s0 < s_end; s0 += UN * R) {
-    Raw8<T> kr[UN], vr[UN];
-    [[maybe_unused]] int po[UN];  // LDS offset of the row's frame in the staged positional embeddings
-#pragma unroll
-    for (int u = 0; u < UN; ++u) {
-      const int s = min(min(s0 + u * R, s_end - 1), S - 1);  // clamp: rows past the end are loaded but not used
-      const int tf = (int)div_patches.div((uint32_t)s);
-      const int64_t off = (int64_t)tf * lay.frame_stride + (int64_t)(s - tf * patches) * lay.row_stride;
-      kr[u].template load<NT>(kb + off);
-      vr[u].template load<NT>(vb + off);
-      po[u] = (tf - f0) * D;
-    }
-    float pds[UN], pdc[UN], pl1[UN];
-#pragma unroll
-    for (int u = 0; u < UN; ++u) {
-      float ds = 0.f, dc = 0.f, l1 = 0.f;
-      [[maybe_unused]] float pe[8];
-      if constexpr (POS) Ld8<float>::load(pb + po[u], pe);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) key_channel(POS ? kr[u].get(e) + pe[e] : kr[u].get(e), qs[e], qc[e], ds, dc, l1);
-      pds[u] = ds;
-      pdc[u] = dc;
-      pl1[u] = l1;
-    }
-    const float ds = group8_reduce_scatter(pds, sub), dc = group8_reduce_scatter(pdc, sub), l1 = group8_reduce_scatter(pl1, sub);
-    // my row of this trip
-    const int s_me = s0 + sub * R;
-    const bool ok = s_me < s_end && mb[div_patches.div((uint32_t)min(s_me, S - 1))] != 0;
+    Raw8<T> vr[UN];
+    int po[UN];  // LDS offset of the row's frame in the staged positional embeddings
+    const KeyRow me = key_trip<T, POS, NT, true>(sp, ln, qs, qc, kb, vb, s0, vr, po);
+    const bool ok = me.ok;
     float p;
     if (ext_w != nullptr) {
       // attn_mode: the softmax-branch weight was computed by the grouped-softmax pass
-      p = ok ? ext_w[((int64_t)b * heads + hd) * S + s_me] : 0.f;
+      p = ok ? ext_w[((int64_t)b * heads + hd) * S + me.s] : 0.f;
     } else {
-      const float m_new = fmaxf(mx, group8_max(ok ? ds : -INFINITY));
+      const float m_new = fmaxf(mx, group8_max(ok ? me.ds : -INFINITY));
       if (m_new != mx) {  // uniform over the group; exp(-inf) = 0 the first time
         const float alpha = __expf(mx - m_new);
         l_own *= alpha;
@@ -119,15 +69,15 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 512 ? (POS ? 2 : 3) : 4)) void decod
         for (int e = 0; e < 8; ++e) as[e] *= alpha;
         mx = m_new;
       }
-      p = ok ? __expf(ds - mx) : 0.f;
+      p = ok ? __expf(me.ds - mx) : 0.f;
       l_own += p;
     }
-    const float c = ok ? coda_weight(dc, l1) : 0.f;  // tanh(dc) · 2·sigmoid(−l1/√d)
+    const float c = ok ? coda_weight(me.dc, me.l1) : 0.f;  // tanh(dc) · 2·sigmoid(−l1/√d)
 #pragma unroll
     for (int u = 0; u < UN; ++u) {
-      const float pu = __shfl(p, lane_base + u, 64), cu = __shfl(c, lane_base + u, 64);
+      const float pu = __shfl(p, ln.lane_base + u, 64), cu = __shfl(c, ln.lane_base + u, 64);
       [[maybe_unused]] float pe[8];
-      if constexpr (POS) Ld8<float>::load(pb + po[u], pe);
+      if constexpr (POS) Ld8<float>::load(sp.pb + po[u], pe);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const float vv = POS ? vr[u].get(e) + pe[e] : vr[u].get(e);
@@ -220,10 +170,9 @@ __global__ __launch_bounds__(1024) void decoder_rowdot_kernel(const float* __res
                                                               float* __restrict__ out, float scale, float fill, int splits,
                                                               int T_frames, int patches, int heads, int R, KvLayout lay,
                                                               FastDiv div_patches) {
-  const int tpr = heads * 8;
+  const HeadLanes ln(heads);
+  const int hd = ln.hd, sub = ln.sub;
   const int b = blockIdx.y, split = blockIdx.x;
-  const int rs = threadIdx.x / tpr, tr = threadIdx.x % tpr;
-  const int hd = tr >> 3, sub = tr & 7;
   const int S = T_frames * patches;
   const int D = heads * HD;
   const int per = (S + splits - 1) / splits;
@@ -235,12 +184,12 @@ __global__ __launch_bounds__(1024) void decoder_rowdot_kernel(const float* __res
 #pragma unroll
     for (int e = 0; e < 8; ++e) av[e] = ap[e] * scale;
   }
-  const T* xb = X + (int64_t)b * T_frames * lay.frame_stride + hd * HD + sub * 8;
-  const float* pb = lay.pos ? lay.pos + hd * HD + sub * 8 : nullptr;
-  for (int s = s_begin + rs; s < s_end; s += R) {
+  const T* xb = ln.channels(X + (int64_t)b * T_frames * lay.frame_stride);
+  const float* pb = lay.pos ? ln.channels(lay.pos) : nullptr;
+  for (int s = s_begin + ln.rs; s < s_end; s += R) {
     float xx[8];
-    const int tf = (int)div_patches.div((uint32_t)s);
-    Ld8<T>::load(xb + (int64_t)tf * lay.frame_stride + (int64_t)(s - tf * patches) * lay.row_stride, xx);
+    int tf;
+    Ld8<T>::load(xb + kv_row_offset(s, patches, lay, div_patches, tf), xx);
     if (pb != nullptr) {
       float pe[8];
       Ld8<float>::load(pb + (int64_t)tf * D, pe);
@@ -475,13 +424,6 @@ void linear_t_plan(int N, int K, int* rows_per_wave, int* ksplit) {
   *ksplit = (K + 31) / 32;
 }
 
-int rows_per_block(int heads) {
-  const int tpr = heads * 8;
-  int R = (256 + tpr - 1) / tpr;
-  while ((tpr * R) % 64 != 0) ++R;
-  return R;
-}
-
 }  // namespace
 
 extern "C" size_t dfd_decoder_attn_workspace(int B, int heads, int d, int splits) {
@@ -489,24 +431,13 @@ extern "C" size_t dfd_decoder_attn_workspace(int B, int heads, int d, int splits
   return (size_t)B * splits * heads * PART * sizeof(float);
 }
 
-// layout checks shared by the decoder attention entry points
-static int check_kv_layout(const char* who, const dfd_kv_layout_t* l, int kv_dtype, int D) {
-  if (l == nullptr) return DFD_OK;
-  const int per16 = kv_dtype == DFD_F32 ? 4 : 8;
-  DFD_REQUIRE(l->row_stride >= D && l->frame_stride > 0 && l->row_stride % per16 == 0 && l->frame_stride % per16 == 0,
-              "%s: key/value layout: row stride %lld, frame stride %lld (elements; rows must stay 16-byte aligned)", who,
-              (long long)l->row_stride, (long long)l->frame_stride);
-  DFD_REQUIRE(!l->pos || dfd_aligned16(l->pos), "%s: the positional embedding must be 16-byte aligned", who);
-  return DFD_OK;
-}
-
 extern "C" int dfd_decoder_attn_fwd(const float* q, const void* k, const void* v, int kv_dtype, const dfd_kv_layout_t* layout,
                                     const uint8_t* frame_mask, const float* ext_weights, float* mix, float* mix_softmax,
                                     float* stats, void* workspace, int splits, int B, int T, int patches, int heads, int d,
                                     void* stream) {
-  DFD_REQUIRE(q && k && v && frame_mask && mix && stats && workspace, "dfd_decoder_attn_fwd: null pointer");
-  DFD_REQUIRE(d == HD, "dfd_decoder_attn_fwd: head dim %d, only 64 is supported", d);
-  DFD_REQUIRE(B >= 0 && T > 0 && patches > 0 && heads > 0 && heads * HD <= 1024, "dfd_decoder_attn_fwd: bad shape");
+  if (int rc = check_decoder_attn("dfd_decoder_attn_fwd", q && k && v && frame_mask && mix && stats && workspace, {k, v, q}, kv_dtype,
+                                  layout, B, T, patches, heads, d))
+    return rc;
   DFD_REQUIRE(splits > 0 && splits <= 4096, "dfd_decoder_attn_fwd: splits=%d", splits);
   // decoder_attn_combine_kernel keeps one rescale weight per (head, split) in LDS beside its two static rows; what no
   // launch can get is refused here, before the partial kernel is launched, rather than by the combine launch
@@ -514,84 +445,52 @@ extern "C" int dfd_decoder_attn_fwd(const float* q, const void* k, const void* v
   DFD_REQUIRE(combine_lds + combine_static <= 160 * 1024,
               "dfd_decoder_attn_fwd: splits=%d with heads=%d needs %zu B of LDS to merge (heads*splits <= 40928)", splits, heads,
               combine_lds);
-  DFD_REQUIRE(kv_dtype == DFD_F32 || kv_dtype == DFD_BF16, "dfd_decoder_attn_fwd: kv_dtype=%d", kv_dtype);
-  DFD_REQUIRE(dfd_aligned16(k) && dfd_aligned16(v) && dfd_aligned16(q), "dfd_decoder_attn_fwd: pointers must be 16-byte aligned");
-  if (int rc = check_kv_layout("dfd_decoder_attn_fwd", layout, kv_dtype, heads * HD)) return rc;
   if (B == 0) return DFD_OK;
   const KvLayout lay = dfd_kv_layout(layout, patches, heads * HD);
   const FastDiv divp = FastDiv::make((uint32_t)patches);
-  const int R = rows_per_block(heads);
-  const int threads = heads * 8 * R;
-  DFD_REQUIRE(threads <= 1024, "dfd_decoder_attn_fwd: heads=%d needs %d threads", heads, threads);
+  const AttnBlock blk = decoder_attn_block(heads);
   const int S_ = T * patches, per_ = (S_ + splits - 1) / splits;
   const int span = lay.pos ? (per_ + patches - 2) / patches + 1 : 0;  // frames a block's rows can touch
-  const size_t lds = (size_t)threads * 18 * sizeof(float) + (size_t)(span < T ? span : T) * heads * HD * sizeof(float);
+  const size_t lds = (size_t)blk.threads * 18 * sizeof(float) + (size_t)(span < T ? span : T) * heads * HD * sizeof(float);
   DFD_REQUIRE(lds <= 160 * 1024, "dfd_decoder_attn_fwd: %zu B of LDS (use more splits)", lds);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const dim3 grid(splits, B), block(threads);
   float* ws = static_cast<float*>(workspace);
-  const bool nt = dfd_stream_on(DFD_STREAM_DECODER_KV);
-#define PARTIAL_LAUNCH2(KT, MT, PS, NT)                                                                              \
-  do {                                                                                                               \
-    if (lds > 64 * 1024)                                                                                             \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&decoder_attn_partial_kernel<KT, MT, PS, NT>),          \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                               \
-    hipLaunchKernelGGL((decoder_attn_partial_kernel<KT, MT, PS, NT>), grid, block, lds, st, q, static_cast<const KT*>(k), \
-                       static_cast<const KT*>(v), frame_mask, ext_weights, ws, splits, T, patches, heads, R, lay, divp); \
-  } while (0)
-#define PARTIAL_LAUNCH1(KT, MT, PS)                                                                                  \
-  do {                                                                                                               \
-    if (nt) PARTIAL_LAUNCH2(KT, MT, PS, true); else PARTIAL_LAUNCH2(KT, MT, PS, false);                              \
-  } while (0)
-#define PARTIAL_LAUNCH(KT, MT)                                                                                       \
-  do {                                                                                                               \
-    if (lay.pos) PARTIAL_LAUNCH1(KT, MT, true); else PARTIAL_LAUNCH1(KT, MT, false);                                 \
-  } while (0)
-  if (kv_dtype == DFD_F32) { if (threads <= 512) PARTIAL_LAUNCH(float, 512); else PARTIAL_LAUNCH(float, 1024); }
-  else { if (threads <= 512) PARTIAL_LAUNCH(bf16_t, 512); else PARTIAL_LAUNCH(bf16_t, 1024); }
-#undef PARTIAL_LAUNCH
-#undef PARTIAL_LAUNCH1
-#undef PARTIAL_LAUNCH2
-  DFD_CHECK_LAUNCH("dfd_decoder_attn_fwd(partial)");
-  if (combine_lds + combine_static > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&decoder_attn_combine_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)combine_lds);
-  hipLaunchKernelGGL(decoder_attn_combine_kernel, dim3(B), dim3(heads * HD), combine_lds, st, ws, mix,
-                     mix_softmax, stats, splits, heads);
-  DFD_CHECK_LAUNCH("dfd_decoder_attn_fwd(combine)");
-  return DFD_OK;
+  const int rc = decoder_attn_dispatch(
+      kv_dtype, blk.threads, lay.pos != nullptr, dfd_stream_on(DFD_STREAM_DECODER_KV), [&](auto kt, auto mt, auto ps, auto nt) {
+        using KT = typename decltype(kt)::type;
+        return launch_kernel("dfd_decoder_attn_fwd(partial)",
+                             decoder_attn_partial_kernel<KT, decltype(mt)::value, decltype(ps)::value, decltype(nt)::value>,
+                             Launch{dim3(splits, B), dim3(blk.threads), lds, st}, q, k, v, frame_mask, ext_weights, ws, splits, T,
+                             patches, heads, blk.R, lay, divp);
+      });
+  if (rc != DFD_OK) return rc;
+  return launch_kernel("dfd_decoder_attn_fwd(combine)", decoder_attn_combine_kernel,
+                       Launch{dim3(B), dim3(heads * HD), combine_lds, st, combine_static}, ws, mix, mix_softmax, stats, splits, heads);
 }
 
-// shared by the attn_mode entry points (also used from decoder_bwd.hip through dfd_decoder_rowdot)
+// shared by the attn_mode entry points (declared in decoder_common.hpp for decoder_bwd.hip)
 int dfd_decoder_rowdot(const float* a, int a_stride, const void* X, int kv_dtype, const dfd_kv_layout_t* layout,
                        const uint8_t* frame_mask, float* out, float scale, float fill, int B, int T, int patches, int heads,
                        hipStream_t st) {
   const KvLayout lay = dfd_kv_layout(layout, patches, heads * HD);
   const FastDiv divp = FastDiv::make((uint32_t)patches);
-  const int R = rows_per_block(heads);
-  const int threads = heads * 8 * R;
+  const AttnBlock blk = decoder_attn_block(heads);
   const int S = T * patches;
   const int splits = max(1, min(S / 64, max(1, 768 / max(B, 1))));
-  const dim3 grid(splits, B), block(threads);
-  if (kv_dtype == DFD_F32)
-    hipLaunchKernelGGL((decoder_rowdot_kernel<float>), grid, block, 0, st, a, a_stride, static_cast<const float*>(X), frame_mask,
-                       out, scale, fill, splits, T, patches, heads, R, lay, divp);
-  else
-    hipLaunchKernelGGL((decoder_rowdot_kernel<bf16_t>), grid, block, 0, st, a, a_stride, static_cast<const bf16_t*>(X),
-                       frame_mask, out, scale, fill, splits, T, patches, heads, R, lay, divp);
-  DFD_CHECK_LAUNCH("dfd_decoder_rowdot");
-  return DFD_OK;
+  return pick(kv_dtype == DFD_F32, [&](auto f32) {
+    using KT = std::conditional_t<decltype(f32)::value, float, bf16_t>;
+    return launch_kernel("dfd_decoder_rowdot", decoder_rowdot_kernel<KT>, Launch{dim3(splits, B), dim3(blk.threads), 0, st}, a,
+                         a_stride, X, frame_mask, out, scale, fill, splits, T, patches, heads, blk.R, lay, divp);
+  });
 }
 
 extern "C" int dfd_decoder_attn_modes_fwd(const float* q, const void* k, int kv_dtype, const dfd_kv_layout_t* layout,
                                           const uint8_t* frame_mask, int modes, float* scores, float* weights, int B, int T,
                                           int patches, int heads, int d, void* stream) {
-  DFD_REQUIRE(q && k && frame_mask && scores && weights, "dfd_decoder_attn_modes_fwd: null pointer");
-  DFD_REQUIRE(d == HD, "dfd_decoder_attn_modes_fwd: head dim %d, only 64 is supported", d);
-  DFD_REQUIRE(B >= 0 && T > 0 && patches > 0 && heads > 0 && heads * HD <= 1024, "dfd_decoder_attn_modes_fwd: bad shape");
+  if (int rc = check_decoder_attn("dfd_decoder_attn_modes_fwd", q && k && frame_mask && scores && weights, {k, q}, kv_dtype, layout, B,
+                                  T, patches, heads, d))
+    return rc;
   DFD_REQUIRE(modes >= 1 && modes <= 3, "dfd_decoder_attn_modes_fwd: modes=%d (bit 0 frame, bit 1 temporal)", modes);
-  DFD_REQUIRE(kv_dtype == DFD_F32 || kv_dtype == DFD_BF16, "dfd_decoder_attn_modes_fwd: kv_dtype=%d", kv_dtype);
-  DFD_REQUIRE(dfd_aligned16(k) && dfd_aligned16(q), "dfd_decoder_attn_modes_fwd: pointers must be 16-byte aligned");
   const size_t lds = (size_t)2 * T * patches * sizeof(float);
   // one ceiling for the pair: dfd_decoder_attn_modes_bwd keeps three floats per key, and a forward it cannot follow is refused
   DFD_REQUIRE((size_t)3 * T * patches * sizeof(float) <= 150 * 1024,
@@ -599,14 +498,9 @@ extern "C" int dfd_decoder_attn_modes_fwd(const float* q, const void* k, int kv_
   if (B == 0) return DFD_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
   // softmax-branch scores q_s·k/√d, -inf on padded frames (models.py:103-104); q holds [softmax | CoDA] per head
-  if (int rc = check_kv_layout("dfd_decoder_attn_modes_fwd", layout, kv_dtype, heads * HD)) return rc;
-  const int rc = dfd_decoder_rowdot(q, 2 * HD, k, kv_dtype, layout, frame_mask, scores, 0.125f, -INFINITY, B, T, patches, heads, st);
-  if (rc != DFD_OK) return rc;
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&decoder_modes_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(decoder_modes_fwd_kernel, dim3(heads, B), dim3(256), lds, st, scores, weights, modes, T, patches);
-  DFD_CHECK_LAUNCH("dfd_decoder_attn_modes_fwd");
-  return DFD_OK;
+  if (int rc = dfd_decoder_rowdot(q, 2 * HD, k, kv_dtype, layout, frame_mask, scores, 0.125f, -INFINITY, B, T, patches, heads, st)) return rc;
+  return launch_kernel("dfd_decoder_attn_modes_fwd", decoder_modes_fwd_kernel, Launch{dim3(heads, B), dim3(256), lds, st}, scores,
+                       weights, modes, T, patches);
 }
 
 extern "C" int dfd_linear_rows(const float* x, int64_t ldx, const float* W, const float* bias, float* y, int64_t ldy,

@@ -15,8 +15,6 @@
 
 namespace {
 
-constexpr int HD = 64;
-
 __device__ __forceinline__ float sgn(float x) { return (float)(x > 0.f) - (float)(x < 0.f); }
 
 // grid (T, B).  part layout per (b, t): [heads][128] dq (softmax query | CoDA query), then [heads*64] dpos.
@@ -32,10 +30,9 @@ __global__ __launch_bounds__(MAXT) void decoder_attn_bwd_kernel(const float* __r
                                                                 G* __restrict__ dk_out, G* __restrict__ dv_out,
                                                                 int T_frames, int patches, int heads, int R, KvLayout lay) {
   extern __shared__ float red[];  // [R][tpr][24]
-  const int tpr = heads * 8;
+  const HeadLanes ln(heads);
+  const int tpr = ln.tpr, rs = ln.rs, tr = ln.tr, hd = ln.hd, sub = ln.sub;
   const int t = blockIdx.x, b = blockIdx.y;
-  const int rs = threadIdx.x / tpr, tr = threadIdx.x % tpr;
-  const int hd = tr >> 3, sub = tr & 7;
   const int D = heads * HD;
   const int S = T_frames * patches;
   float* dst = part + ((int64_t)b * T_frames + t) * (3 * D);
@@ -43,13 +40,11 @@ __global__ __launch_bounds__(MAXT) void decoder_attn_bwd_kernel(const float* __r
 
   float qs[8], qc[8], dm[8], dqs[8], dqc[8], sv[8];
   float a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  load_query(q, b, heads, ln, 1.0f, qs, qc);  // unscaled: qs enters the gradients as it is
   {
-    const float* qp = q + ((int64_t)b * heads + hd) * (2 * HD) + sub * 8;
-    const float* dp = dmix + (int64_t)b * D + hd * HD + sub * 8;
+    const float* dp = ln.channels(dmix + (int64_t)b * D);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      qs[e] = qp[e];
-      qc[e] = qp[HD + e];
       dm[e] = dp[e];
       dqs[e] = dqc[e] = sv[e] = 0.f;
     }
@@ -59,7 +54,7 @@ __global__ __launch_bounds__(MAXT) void decoder_attn_bwd_kernel(const float* __r
   const bool ext = ext_w != nullptr;
   float dlt = 0.f, M = 0.f, invL = 1.f;
   if (!ext) {
-    const float* mp = mix_s + (int64_t)b * D + hd * HD + sub * 8;
+    const float* mp = ln.channels(mix_s + (int64_t)b * D);
 #pragma unroll
     for (int e = 0; e < 8; ++e) dlt = fmaf(dm[e], mp[e], dlt);
     dlt = 0.5f * group8_sum(dlt);
@@ -70,38 +65,36 @@ __global__ __launch_bounds__(MAXT) void decoder_attn_bwd_kernel(const float* __r
   if (valid) {
     const int s0 = t * patches;
     // this block's frame: rows j*row_stride of frame b*T + t (KvLayout), plus the frame's positional embedding
-    const T* kb = k + ((int64_t)b * T_frames + t) * lay.frame_stride + hd * HD + sub * 8;
-    const T* vb = v + ((int64_t)b * T_frames + t) * lay.frame_stride + hd * HD + sub * 8;
+    const T* kb = ln.channels(k + ((int64_t)b * T_frames + t) * lay.frame_stride);
+    const T* vb = ln.channels(v + ((int64_t)b * T_frames + t) * lay.frame_stride);
     float pe[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) pe[e] = 0.f;
-    if (lay.pos != nullptr) Ld8<float>::load(lay.pos + (int64_t)t * D + hd * HD + sub * 8, pe);
+    if (lay.pos != nullptr) Ld8<float>::load(ln.channels(lay.pos + (int64_t)t * D), pe);
     // Four rows per trip, all eight loads issued before the first use (the trip is a latency chain otherwise).
     // Every lane forms its 8-channel share of the four dot products of the four rows; a reduce-scatter over the
     // 8-lane head group leaves lanes j and j+4 with the totals of row j, so a row's transcendentals and divisions
     // (the VALU bulk here) run on two lanes instead of eight; its three gradient scalars travel back to the group
     // for the per-channel accumulation.
-    constexpr int UN = 4;
-    const int lane_base = (threadIdx.x & 63) & ~7;
+    constexpr int UN4 = 4;
+    const int lane_base = ln.lane_base;
     float a1o = 0.f, a2o = 0.f, a3o = 0.f;  // sums over the rows lanes 0..3 of the group finished
-    for (int j0 = rs; j0 < patches; j0 += UN * R) {
-      Raw8<T> kq[UN], vq[UN];
+    for (int j0 = rs; j0 < patches; j0 += UN4 * R) {
+      Raw8<T> kq[UN4], vq[UN4];
 #pragma unroll
-      for (int u = 0; u < UN; ++u) {
+      for (int u = 0; u < UN4; ++u) {
         const int j = min(j0 + u * R, patches - 1);
         kq[u].template load<NT>(kb + (int64_t)j * lay.row_stride);
         vq[u].template load<NT>(vb + (int64_t)j * lay.row_stride);
       }
-      float ps[UN], pt[UN], pl[UN], pw[UN];
+      float ps[UN4], pt[UN4], pl[UN4], pw[UN4];
 #pragma unroll
-      for (int u = 0; u < UN; ++u) {
+      for (int u = 0; u < UN4; ++u) {
         float s = 0.f, tt = 0.f, l1 = 0.f, dw = 0.f;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           const float kk = kq[u].get(e) + pe[e], vv = vq[u].get(e) + pe[e];
-          s = fmaf(qs[e] * 0.125f, kk, s);
-          tt = fmaf(qc[e] * 0.125f, kk, tt);
-          l1 += fabsf(qc[e] - kk);
+          key_channel(kk, qs[e] * 0.125f, qc[e], s, tt, l1);
           dw = fmaf(dm[e], vv, dw);
         }
         ps[u] = s; pt[u] = tt; pl[u] = l1; pw[u] = dw;
@@ -113,9 +106,7 @@ __global__ __launch_bounds__(MAXT) void decoder_attn_bwd_kernel(const float* __r
       const bool ok = jm < patches;
       const int64_t wi = ((int64_t)b * heads + hd) * S + s0 + min(jm, patches - 1);
       const float aw = ext ? ext_w[wi] : __expf(s - M) * invL;      // softmax(-branch) weight
-      const float g = 2.0f / (1.0f + __expf(l1 * 0.125f));         // 2·sigmoid(−l1/8)
-      const float e2 = __expf(2.0f * tt);
-      const float th = 1.0f - 2.0f / (e2 + 1.0f);                  // tanh
+      const float g = coda_gate(l1), th = fast_tanh(tt);            // the CoDA weight's two factors
       const float w = ok ? 0.5f * (aw + th * g) : 0.f;
       const float dc = 0.5f * dw;
       const float ds = ok ? (ext ? ext_ds[wi] : aw * (0.5f * dw - dlt)) : 0.f;
@@ -127,7 +118,7 @@ __global__ __launch_bounds__(MAXT) void decoder_attn_bwd_kernel(const float* __r
         a3o += w;
       }
 #pragma unroll
-      for (int u = 0; u < UN; ++u) {
+      for (int u = 0; u < UN4; ++u) {
         const float dsu = __shfl(ds, lane_base + u, 64), dtu = __shfl(dt, lane_base + u, 64), dLu = __shfl(dL, lane_base + u, 64);
         float dkk[8];
 #pragma unroll
@@ -413,13 +404,6 @@ __global__ void head_dproj_kernel(const float* __restrict__ feat, const float* _
   dproj[idx] = s;
 }
 
-int rows_per_block(int heads) {
-  const int tpr = heads * 8;
-  int R = (256 + tpr - 1) / tpr;
-  while ((tpr * R) % 64 != 0) ++R;
-  return R;
-}
-
 }  // namespace
 
 extern "C" size_t dfd_decoder_attn_bwd_workspace(int B, int T, int heads, int d) {
@@ -433,88 +417,52 @@ extern "C" int dfd_decoder_attn_bwd(const float* q, const void* k, const void* v
                                     const float* ext_weights, const float* ext_dscores, float* dq, float* dpos, void* dk,
                                     void* dv, int dkv_dtype, void* workspace, int B, int T, int patches, int heads, int d,
                                     void* stream) {
-  DFD_REQUIRE(q && k && v && frame_mask && dmix && dq && workspace, "dfd_decoder_attn_bwd: null pointer");
+  if (int rc = check_decoder_attn("dfd_decoder_attn_bwd", q && k && v && frame_mask && dmix && dq && workspace, {k, v}, kv_dtype, layout,
+                                  B, T, patches, heads, d))
+    return rc;
   DFD_REQUIRE(!ext_weights == !ext_dscores, "dfd_decoder_attn_bwd: ext_weights and ext_dscores go together");
   DFD_REQUIRE(ext_weights || (mix_softmax && stats), "dfd_decoder_attn_bwd: mix_softmax and stats are required without ext_weights");
-  DFD_REQUIRE(d == HD, "dfd_decoder_attn_bwd: head dim %d, only 64 is supported", d);
-  DFD_REQUIRE(B >= 0 && T > 0 && patches > 0 && heads > 0 && heads * HD <= 1024, "dfd_decoder_attn_bwd: bad shape");
-  DFD_REQUIRE(kv_dtype == DFD_F32 || kv_dtype == DFD_BF16, "dfd_decoder_attn_bwd: kv_dtype=%d", kv_dtype);
   DFD_REQUIRE(!dk == !dv, "dfd_decoder_attn_bwd: dk and dv must both be given or both be NULL");
   DFD_REQUIRE(!dk || dkv_dtype == DFD_F32 || dkv_dtype == DFD_BF16, "dfd_decoder_attn_bwd: dkv_dtype=%d", dkv_dtype);
-  DFD_REQUIRE(dfd_aligned16(k) && dfd_aligned16(v), "dfd_decoder_attn_bwd: k and v must be 16-byte aligned");
-  if (layout != nullptr) {
-    const int per16 = kv_dtype == DFD_F32 ? 4 : 8;
-    DFD_REQUIRE(layout->row_stride >= heads * HD && layout->frame_stride > 0 && layout->row_stride % per16 == 0 &&
-                    layout->frame_stride % per16 == 0 && (!layout->pos || dfd_aligned16(layout->pos)),
-                "dfd_decoder_attn_bwd: key/value layout: row stride %lld, frame stride %lld (elements; 16-byte aligned rows)",
-                (long long)layout->row_stride, (long long)layout->frame_stride);
-  }
   if (B == 0) return DFD_OK;
   const KvLayout lay = dfd_kv_layout(layout, patches, heads * HD);
-  const int R = rows_per_block(heads);
-  const int threads = heads * 8 * R;
-  const size_t lds = (size_t)threads * 24 * sizeof(float);
+  const AttnBlock blk = decoder_attn_block(heads);
+  const size_t lds = (size_t)blk.threads * 24 * sizeof(float);
   const int D = heads * HD;
   hipStream_t st = static_cast<hipStream_t>(stream);
   float* part = static_cast<float*>(workspace);
-  const dim3 grid(T, B), block(threads);
-  const bool nt = dfd_stream_on(DFD_STREAM_DECODER_KV);
-#define BWD_LAUNCH2(KT, GT, MT, NT)                                                                                          \
-  do {                                                                                                                      \
-    if (lds > 64 * 1024)                                                                                                    \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&decoder_attn_bwd_kernel<KT, GT, MT, NT>),                     \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                      \
-    hipLaunchKernelGGL((decoder_attn_bwd_kernel<KT, GT, MT, NT>), grid, block, lds, st, q, static_cast<const KT*>(k),          \
-                       static_cast<const KT*>(v), frame_mask, dmix, mix_softmax, stats, ext_weights, ext_dscores, part,      \
-                       static_cast<GT*>(dk), static_cast<GT*>(dv), T, patches, heads, R, lay);                                    \
-  } while (0)
-#define BWD_LAUNCH1(KT, GT, MT)                                                                                              \
-  do {                                                                                                                      \
-    if (nt) BWD_LAUNCH2(KT, GT, MT, true); else BWD_LAUNCH2(KT, GT, MT, false);                                             \
-  } while (0)
-  // blocks of <= 512 threads (every even head count) get the 256-register budget: no spills with two rows in flight
-#define BWD_LAUNCH(KT, GT)                                                                                                  \
-  do {                                                                                                                      \
-    if (threads <= 512) BWD_LAUNCH1(KT, GT, 512); else BWD_LAUNCH1(KT, GT, 1024);                                           \
-  } while (0)
-  const bool gb = dk && dkv_dtype == DFD_BF16;
-  if (kv_dtype == DFD_F32) { if (gb) BWD_LAUNCH(float, bf16_t); else BWD_LAUNCH(float, float); }
-  else { if (gb) BWD_LAUNCH(bf16_t, bf16_t); else BWD_LAUNCH(bf16_t, float); }
-#undef BWD_LAUNCH1
-#undef BWD_LAUNCH2
-#undef BWD_LAUNCH
-  DFD_CHECK_LAUNCH("dfd_decoder_attn_bwd");
+  // blocks of <= 512 threads (every even head count) get the 256-register budget: no spills with two rows in flight; the
+  // kernel reads `pos` through the layout (no POS form)
+  const int rc = pick(dk && dkv_dtype == DFD_BF16, [&](auto gb) {
+    using GT = std::conditional_t<decltype(gb)::value, bf16_t, float>;
+    return decoder_attn_dispatch(kv_dtype, blk.threads, false, dfd_stream_on(DFD_STREAM_DECODER_KV), [&](auto kt, auto mt, auto, auto nt) {
+      using KT = typename decltype(kt)::type;
+      return launch_kernel("dfd_decoder_attn_bwd", decoder_attn_bwd_kernel<KT, GT, decltype(mt)::value, decltype(nt)::value>,
+                           Launch{dim3(T, B), dim3(blk.threads), lds, st}, q, k, v, frame_mask, dmix, mix_softmax, stats, ext_weights,
+                           ext_dscores, part, dk, dv, T, patches, heads, blk.R, lay);
+    });
+  });
+  if (rc != DFD_OK) return rc;
   const int total = B * 2 * D + (dpos ? T * D : 0);
-  hipLaunchKernelGGL(decoder_attn_bwd_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, st, part, dq, dpos, B, T, D);
-  DFD_CHECK_LAUNCH("dfd_decoder_attn_bwd(reduce)");
-  return DFD_OK;
+  return launch_kernel("dfd_decoder_attn_bwd(reduce)", decoder_attn_bwd_reduce_kernel, Launch{dim3((total + 255) / 256), dim3(256), 0, st},
+                       part, dq, dpos, B, T, D);
 }
-
-int dfd_decoder_rowdot(const float* a, int a_stride, const void* X, int kv_dtype, const dfd_kv_layout_t* layout,
-                       const uint8_t* frame_mask, float* out, float scale, float fill, int B, int T, int patches, int heads,
-                       hipStream_t st);  // decoder.hip
 
 extern "C" int dfd_decoder_attn_modes_bwd(const float* scores, const void* v, int kv_dtype, const dfd_kv_layout_t* layout,
                                           const float* dmix, int modes, float* dwv_workspace, float* dscores, int B, int T,
                                           int patches, int heads, int d, void* stream) {
-  DFD_REQUIRE(scores && v && dmix && dwv_workspace && dscores, "dfd_decoder_attn_modes_bwd: null pointer");
-  DFD_REQUIRE(d == HD, "dfd_decoder_attn_modes_bwd: head dim %d, only 64 is supported", d);
-  DFD_REQUIRE(B >= 0 && T > 0 && patches > 0 && heads > 0 && heads * HD <= 1024, "dfd_decoder_attn_modes_bwd: bad shape");
+  if (int rc = check_decoder_attn("dfd_decoder_attn_modes_bwd", scores && v && dmix && dwv_workspace && dscores, {v, dmix}, kv_dtype,
+                                  layout, B, T, patches, heads, d))
+    return rc;
   DFD_REQUIRE(modes >= 1 && modes <= 3, "dfd_decoder_attn_modes_bwd: modes=%d (bit 0 frame, bit 1 temporal)", modes);
-  DFD_REQUIRE(kv_dtype == DFD_F32 || kv_dtype == DFD_BF16, "dfd_decoder_attn_modes_bwd: kv_dtype=%d", kv_dtype);
-  DFD_REQUIRE(dfd_aligned16(v) && dfd_aligned16(dmix), "dfd_decoder_attn_modes_bwd: pointers must be 16-byte aligned");
   const size_t lds = (size_t)3 * T * patches * sizeof(float);
   DFD_REQUIRE(lds <= 150 * 1024, "dfd_decoder_attn_modes_bwd: T*patches=%d too large for one LDS pass", T * patches);
   if (B == 0) return DFD_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
   // dL/d(weight of key s) = dmix · v_s  (weights multiply v in the mix, models.py:144)
-  const int rc = dfd_decoder_rowdot(dmix, HD, v, kv_dtype, layout, nullptr, dwv_workspace, 1.0f, 0.f, B, T, patches, heads, st);
-  if (rc != DFD_OK) return rc;
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&decoder_modes_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(decoder_modes_bwd_kernel, dim3(heads, B), dim3(256), lds, st, scores, dwv_workspace, dscores, modes, T, patches);
-  DFD_CHECK_LAUNCH("dfd_decoder_attn_modes_bwd");
-  return DFD_OK;
+  if (int rc = dfd_decoder_rowdot(dmix, HD, v, kv_dtype, layout, nullptr, dwv_workspace, 1.0f, 0.f, B, T, patches, heads, st)) return rc;
+  return launch_kernel("dfd_decoder_attn_modes_bwd", decoder_modes_bwd_kernel, Launch{dim3(heads, B), dim3(256), lds, st}, scores,
+                       dwv_workspace, dscores, modes, T, patches);
 }
 
 extern "C" int dfd_linear_rows_bwd_weight(const float* dy, int64_t lddy, const float* x, int64_t ldx, float* dW, float* db,

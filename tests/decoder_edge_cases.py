@@ -88,7 +88,7 @@ def empty_splits(S, splits):
 
 
 def rows_per_block(heads):
-    """csrc/decoder.hip rows_per_block: key rows side by side in a workgroup of heads*8*R threads, whole waves"""
+    """csrc/decoder_common.hpp decoder_attn_block: key rows side by side in a workgroup of heads*8*R threads, whole waves"""
     tpr = heads * 8
     R = (256 + tpr - 1) // tpr
     while (tpr * R) % 64 != 0:

@@ -47,6 +47,45 @@ def test_invalid_arguments_are_reported_not_launched(lib):
     assert lib.dfd_decoder_attn_workspace(16, 12, 64, 8) == 16 * 8 * 12 * 130 * 4
 
 
+def test_decoder_attention_entry_points_refuse_the_same_arguments(lib):
+    """The five decoder-attention entry points share one argument check (csrc/decoder_common.hpp check_decoder_attn):
+    each refuses every bad argument of the table on the host, under its own name, and accepts the valid call with B = 0.
+    No pointer is dereferenced."""
+    import ctypes
+    p = 1 << 12
+    T, P, H = 2, 3, 2
+    D = H * 64
+
+    def call(name, B=2, d=64, heads=H, dt=capi.F32, kv=p, lay=None):
+        lp = ctypes.byref(lay) if lay is not None else None
+        args = {
+            "dfd_decoder_attn_fwd": (p, kv, kv, dt, lp, p, None, p, None, p, p, 1, B, T, P, heads, d, None),
+            "dfd_decoder_attn_modes_fwd": (p, kv, dt, lp, p, 3, p, p, B, T, P, heads, d, None),
+            "dfd_decoder_attn_map": (p, kv, dt, lp, p, p, None, p, None, B, T, P, heads, d, None),
+            "dfd_decoder_attn_bwd": (p, kv, kv, dt, lp, p, p, p, p, None, None, p, p, None, None, capi.F32, p, B, T, P, heads, d, None),
+            "dfd_decoder_attn_modes_bwd": (p, kv, dt, lp, p, 3, p, p, B, T, P, heads, d, None),
+        }[name]
+        return getattr(lib, name)(*args)
+
+    bad = {
+        "d = 32": dict(d=32),
+        "heads = 17": dict(heads=17),
+        "kv_dtype = 7": dict(dt=7),
+        "K / V pointer off by 8 bytes": dict(kv=p + 8),
+        "row stride 127 < D": dict(lay=capi.KvLayoutDesc(127, 3 * 128, None)),
+        "bf16 row stride 132: not a multiple of 8 elements": dict(dt=capi.BF16, lay=capi.KvLayoutDesc(132, 3 * 136, None)),
+        "frame stride 0": dict(lay=capi.KvLayoutDesc(D, 0, None)),
+        "pos off by 4 bytes": dict(lay=capi.KvLayoutDesc(D, P * D, p + 4)),
+    }
+    for name in ("dfd_decoder_attn_fwd", "dfd_decoder_attn_modes_fwd", "dfd_decoder_attn_map", "dfd_decoder_attn_bwd",
+                 "dfd_decoder_attn_modes_bwd"):
+        for what, kw in bad.items():
+            assert call(name, **kw) == -1, f"{name}: {what} was accepted"
+            assert lib.dfd_last_error().startswith(name.encode() + b":"), (name, what, lib.dfd_last_error())
+        assert call(name, B=0) == 0, (name, lib.dfd_last_error())
+        assert call(name, B=0, dt=capi.BF16, lay=capi.KvLayoutDesc(D + 8, (P + 1) * (D + 8), p)) == 0, (name, lib.dfd_last_error())
+
+
 def test_cpu_tensors_fail_loudly(lib):
     x = torch.zeros(4, 8)
     with pytest.raises(capi.DfdError):
