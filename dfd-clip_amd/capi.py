@@ -193,6 +193,7 @@ HOOK_SIGNATURES = {
     "dfd_gemm_pair_set_variant": (c_int, [c_int]),
     "dfd_gemm_pair_plan": (c_int, [c_int64, c_int, c_int]),
     "dfd_gemm_pair_launches": (c_int64, []),
+    "dfd_gemm_at_b_last_path": (c_int, []),
     "dfd_stream_policy_set": (c_uint, [c_uint]),
     "dfd_stream_policy_get": (c_uint, []),
 }
@@ -522,6 +523,12 @@ def gemm_last_path():
 
 def gemm_at_b_workspace_bytes(R, Ma, Nb, dtype):
     return load_library().dfd_gemm_at_b_workspace(R, Ma, Nb, _DTYPE[dtype])
+
+
+def gemm_at_b_last_path():
+    """128 / 256 when this thread's last gemm_at_b ran on the gemm_tn kernel of that tile width, 1 for the transpose +
+    general-kernel fallback, 0 before any call."""
+    return load_library().dfd_gemm_at_b_last_path()
 
 
 def gemm_at_b(a, b, c, workspace):

@@ -448,7 +448,11 @@ extern "C" int dfd_gemm_fp8(const void* A, int64_t lda, const void* W, int64_t l
 bool dfd_gemm_tn_supported(const void* A, int64_t lda, const void* B, int64_t ldb, int Ma, int Nb);
 int dfd_gemm_tn_splits(int64_t R, int Ma, int Nb);
 int dfd_gemm_tn_launch(const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t R, int Ma, int Nb,
-                       float* slabs, hipStream_t st);
+                       float* slabs, hipStream_t st, int* tile);
+
+// which kernels served this thread's last successful dfd_gemm_at_b (include/dfdclip_hooks.h)
+static thread_local int g_at_b_last_path = 0;
+extern "C" int dfd_gemm_at_b_last_path(void) { return g_at_b_last_path; }
 
 extern "C" size_t dfd_gemm_at_b_workspace(int64_t R, int Ma, int Nb, int dtype) {
   if (R <= 0 || Ma <= 0 || Nb <= 0) return 0;
@@ -472,10 +476,20 @@ extern "C" int dfd_gemm_at_b(const void* A, int64_t lda, const void* B, int64_t 
   DFD_REQUIRE(R > 0 && Ma > 0 && Nb > 0 && lda >= Ma && ldb >= Nb, "dfd_gemm_at_b: bad shape");
   DFD_REQUIRE(R < (int64_t)1 << 31, "dfd_gemm_at_b: R too large");
   DFD_REQUIRE(dtype == DFD_F32 || dtype == DFD_BF16, "dfd_gemm_at_b: dtype=%d", dtype);
+  const bool tn = dtype == DFD_BF16 && dfd_gemm_tn_supported(A, lda, B, ldb, Ma, Nb);
+  // the fallback's transposes put one block of 32 rows on grid.y (gemm_tn.hip puts the rows on no grid axis)
+  DFD_REQUIRE(tn || (R + 31) / 32 <= 65535, "dfd_gemm_at_b: R=%lld needs more than the 65535 grid.y blocks of 32 rows the transpose path can launch",
+              (long long)R);
   DFD_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "dfd_gemm_at_b: workspace must be 256-byte aligned");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == DFD_BF16 && dfd_gemm_tn_supported(A, lda, B, ldb, Ma, Nb))
-    return dfd_gemm_tn_launch(A, lda, B, ldb, C, R, Ma, Nb, static_cast<float*>(workspace), st);
-  if (dtype == DFD_F32) return launch_at_b<float>(A, lda, B, ldb, C, R, Ma, Nb, workspace, st);
-  return launch_at_b<bf16_t>(A, lda, B, ldb, C, R, Ma, Nb, workspace, st);
+  if (tn) {
+    int tile = 0;
+    const int rc = dfd_gemm_tn_launch(A, lda, B, ldb, C, R, Ma, Nb, static_cast<float*>(workspace), st, &tile);
+    if (rc == DFD_OK) g_at_b_last_path = tile;
+    return rc;
+  }
+  const int rc = dtype == DFD_F32 ? launch_at_b<float>(A, lda, B, ldb, C, R, Ma, Nb, workspace, st)
+                                  : launch_at_b<bf16_t>(A, lda, B, ldb, C, R, Ma, Nb, workspace, st);
+  if (rc == DFD_OK) g_at_b_last_path = 1;
+  return rc;
 }

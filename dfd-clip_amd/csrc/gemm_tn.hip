@@ -191,8 +191,9 @@ int dfd_gemm_tn_splits(int64_t R, int Ma, int Nb) {
   return sp;
 }
 
+// *tile = 128 or 256: the tile width that ran (dfd_gemm_at_b_last_path)
 int dfd_gemm_tn_launch(const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t R, int Ma, int Nb,
-                       float* slabs, hipStream_t st) {
+                       float* slabs, hipStream_t st, int* tile) {
   TnArgs a;
   a.A = static_cast<const bf16_t*>(A);
   a.B = static_cast<const bf16_t*>(B);
@@ -218,5 +219,6 @@ int dfd_gemm_tn_launch(const void* A, int64_t lda, const void* B, int64_t ldb, f
   const int64_t n = (int64_t)Ma * Nb;
   hipLaunchKernelGGL(tn_slab_reduce_kernel, dim3((unsigned)((n / 4 + 63) / 64)), dim3(64 * ZG), 0, st, slabs, C, n, splits);
   DFD_CHECK_LAUNCH("dfd_gemm_at_b(reduce)");
+  *tile = tn_tile(Ma, Nb);
   return DFD_OK;
 }

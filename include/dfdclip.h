@@ -191,7 +191,11 @@ int dfd_gemm_set_variant(int variant);
 /* C[Ma, Nb] (f32) = Aᵀ · B for tall row-major operands A [R, Ma], B [R, Nb] in `dtype` — the weight
  * gradient of a Linear applied to R rows (adapter training: R = B·T·patches).  Internally: zero-padded
  * transposes, a split-K pass of the general MFMA kernel into f32 slabs, fixed-order slab reduction
- * (deterministic).  workspace >= dfd_gemm_at_b_workspace(...) bytes, 256-byte aligned. */
+ * (deterministic).  workspace >= dfd_gemm_at_b_workspace(...) bytes, 256-byte aligned.
+ * bf16 operands with Ma % 128 == 0, Nb % 128 == 0, lda % 8 == 0, ldb % 8 == 0 and 16-byte aligned bases skip the
+ * transposes (a transposing LDS read instead) and take any R < 2^31.  Every other call takes the transposes, which put
+ * one block of 32 rows on grid.y: it is refused on the host, before any launch, where ceil(R / 32) > 65535, i.e.
+ * R > 2,097,120. */
 size_t dfd_gemm_at_b_workspace(int64_t R, int Ma, int Nb, int dtype);
 int dfd_gemm_at_b(const void* A, int64_t lda, const void* B, int64_t ldb, int dtype, float* C, int64_t R, int Ma, int Nb,
                   void* workspace, void* stream);

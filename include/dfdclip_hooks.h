@@ -31,6 +31,12 @@ int dfd_gemm_pair_plan(int64_t M, int D, int H);
  * DFD_GEMM_C_BLOCKED or DFD_GEMM_A_BLOCKED in force; not the calls variant 1 turned row-major).  For tests. */
 int64_t dfd_gemm_pair_launches(void);
 
+/* Which kernels served this thread's last successful dfd_gemm_at_b: 128 or 256 = the transposing-LDS-read kernel of
+ * gemm_tn.hip at that tile width (bf16, both extents multiples of 128 resp. 256, ld % 8 == 0, 16-byte aligned bases);
+ * 1 = transposes into the workspace + the general split-K kernel (everything else); 0 = no call yet.  What
+ * dfd_gemm_last_path is to dfd_gemm. */
+int dfd_gemm_at_b_last_path(void);
+
 /* The cache policy of the kernels that touch every byte once.  One bit per family; a set bit makes that family's loads
  * and stores of its read-once (write-once) stream non-temporal, so that they do not evict what the persistent GEMMs of
  * another stream keep in L2.  Results are bit-identical either way (tests/test_hip_stream_policy.py).  Process-wide

@@ -86,6 +86,30 @@ def test_decoder_attention_entry_points_refuse_the_same_arguments(lib):
         assert call(name, B=0, dt=capi.BF16, lay=capi.KvLayoutDesc(D + 8, (P + 1) * (D + 8), p)) == 0, (name, lib.dfd_last_error())
 
 
+def test_gemm_at_b_refuses_rows_the_fallback_cannot_launch(lib):
+    """The transpose + general-kernel path of dfd_gemm_at_b puts one block of 32 rows on grid.y: more than 65535 blocks
+    are refused on the host, under the function's name, before any launch.  No pointer is dereferenced and nothing is
+    launched: the accepted R is stopped by the next argument check (a workspace that is not 256-byte aligned), which a
+    refused R never reaches.  The gemm_tn path (bf16, extents multiples of 128) has no such limit."""
+    p = 1 << 12
+    path_before = lib.dfd_gemm_at_b_last_path()
+
+    def call(R, dtype=capi.F32, Ma=8, Nb=12, ws=p + 16):
+        return lib.dfd_gemm_at_b(p, Ma, p, Nb, dtype, p, R, Ma, Nb, ws, None)
+
+    for dtype in (capi.F32, capi.BF16):
+        assert call(65536 * 32, dtype) == -1
+        err = lib.dfd_last_error()
+        assert err.startswith(b"dfd_gemm_at_b:") and b"65535" in err and b"grid.y" in err, err
+        assert call(65535 * 32 + 1, dtype) == -1 and b"65535" in lib.dfd_last_error()
+        assert call(65535 * 32, dtype) == -1
+        assert lib.dfd_last_error() == b"dfd_gemm_at_b: workspace must be 256-byte aligned", lib.dfd_last_error()
+    # bf16 operands the gemm_tn kernels serve: the limit does not apply
+    assert call(65536 * 32, capi.BF16, Ma=128, Nb=128) == -1
+    assert lib.dfd_last_error() == b"dfd_gemm_at_b: workspace must be 256-byte aligned", lib.dfd_last_error()
+    assert lib.dfd_gemm_at_b_last_path() == path_before  # set on success only
+
+
 def test_cpu_tensors_fail_loudly(lib):
     x = torch.zeros(4, 8)
     with pytest.raises(capi.DfdError):

@@ -592,11 +592,12 @@ def test_gemm_fp8(capi, M, N, K, tok):
 
 # ---- dfd_gemm_at_b ------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("R,Ma,Nb", [(40, 8, 12), (777, 128, 32), (5000, 256, 768)])
+@pytest.mark.parametrize("R,Ma,Nb", [(40, 8, 12), (777, 128, 32), (5000, 256, 768), (1600, 128, 128), (1601, 384, 640), (1600, 256, 256)])
 @pytest.mark.parametrize("dtype", [F32, BF16])
 def test_gemm_at_b(capi, R, Ma, Nb, dtype):
     """R not a multiple of 32, lda = Ma + 8, ldb = Nb + 8 (multiples of 8: the same kernel family as the dense call),
-    the workspace exactly dfd_gemm_at_b_workspace(...) bytes."""
+    the workspace exactly dfd_gemm_at_b_workspace(...) bytes.  The last three: the 128-wide tile of gemm_tn.hip, and an
+    empty last split on either tile width (tests/test_hip_gemm_exact.py)."""
     a, bm = rnd(R, Ma, seed=40).to(dtype), rnd(R, Nb, seed=41).to(dtype)
     want = a.double().T @ bm.double()
     nbytes = capi.gemm_at_b_workspace_bytes(R, Ma, Nb, dtype)
