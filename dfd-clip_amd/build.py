@@ -24,8 +24,10 @@ FLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-
 # spill 2 to 8 registers (8 to 32 bytes per lane); its K loop waits for vmcnt(0) every step, so that only over-waits
 # there, and it is not in the list.  Both kernels inline one epilogue, tile_epilogue in gemm256p_common.hpp.)
 # align.hip has no hand-counted waits; it is listed because a spill in its tap loop would put scratch traffic on a kernel
-# whose whole cost is memory operations.
-NO_SCRATCH = {"gemm256e.hip": "gemm256e_kernel", "attention_mfma_xrow.hip": "attn_mfma_xrow_kernel", "align.hip": "align_crop_u8_kernel"}
+# whose whole cost is memory operations.  elastic.hip's remap kernel is listed for the same reason: it holds sixteen tap
+# offsets and weights per lane across its frame loop (both instantiations are checked).
+NO_SCRATCH = {"gemm256e.hip": "gemm256e_kernel", "attention_mfma_xrow.hip": "attn_mfma_xrow_kernel", "align.hip": "align_crop_u8_kernel",
+              "elastic.hip": "elastic_remap_u8_kernel"}
 
 
 def _hipcc():
@@ -74,6 +76,7 @@ def build(force=False, verbose=False, extra_flags=()):
     headers.append(os.path.join(INCLUDE, "dfdclip_explain.h"))
     headers.append(os.path.join(INCLUDE, "dfdclip_augment.h"))
     headers.append(os.path.join(INCLUDE, "dfdclip_align.h"))
+    headers.append(os.path.join(INCLUDE, "dfdclip_elastic.h"))
     headers.append(os.path.join(INCLUDE, "dfdclip_hooks.h"))
     jobs, objs = [], []
     for src in sources():

@@ -6,7 +6,7 @@ raises.  Tensors are passed as raw device pointers; every call enqueues on
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint, c_uint8, c_uint32, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint, c_uint8, c_uint32, c_uint64, c_void_p
 
 import torch
 
@@ -187,6 +187,14 @@ ALIGN_SIGNATURES = {
                                   c_void_p]),
 }
 
+ELASTIC_MAX_RADIUS, ELASTIC_TAP_ONE, ELASTIC_SITE = 128, 32768, 0xE1A57100
+
+# elastic warp (the reference's `ssl_fake`) beside the ABI, in a header of its own (include/dfdclip_elastic.h)
+ELASTIC_SIGNATURES = {
+    "dfd_elastic_field": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_uint64, c_void_p, c_int, c_int32, c_void_p]),
+    "dfd_elastic_remap_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+}
+
 # test / measurement hooks outside the ABI header (include/dfdclip_hooks.h)
 HOOK_SIGNATURES = {
     "dfd_attention_set_variant": (c_int, [c_int]),
@@ -217,7 +225,7 @@ def load_library(path=None):
         raise DfdError(f"{path} not found: the HIP kernel library is not built and there is no fallback path")
     lib = ctypes.CDLL(path)
     for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **EXPLAIN_SIGNATURES, **AUGMENT_SIGNATURES, **ALIGN_SIGNATURES,
-                               **HOOK_SIGNATURES}.items():
+                               **ELASTIC_SIGNATURES, **HOOK_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError:
@@ -397,6 +405,37 @@ def align_crop_u8(src, out, records, layout, row_stride, frame_stride, win_h, wi
         assert span <= have, f"the strides describe {span} bytes, the tensor's memory holds {have} from its first element on"
     _check(load_library().dfd_align_crop_u8(_ptr(src), int(layout), int(row_stride), int(frame_stride), int(win_h), int(win_w), _ptr(out),
                                             n, oh, ow, _ptr(records), ALIGN_SWAP_RB if swap_rb else 0, _stream()), "dfd_align_crop_u8")
+    return out
+
+
+def elastic_field(field, field_ids, seed, taps, alpha_q):
+    """field[f] = the displacement field with id field_ids[f] (include/dfdclip_elastic.h): field i16 [n,H,W,2] on the device
+    ((dx5, dy5) in 1/32-pixel units), field_ids i64 [n] on the device, `seed` a 64-bit integer, `taps` a HOST int32 array of
+    2 * radius + 1 Q15 weights summing to 32768, alpha_q = round(256 * alpha)."""
+    _dev(field, field_ids)
+    assert field.dtype == torch.int16 and field.dim() == 4 and field.shape[3] == 2 and field.is_contiguous()
+    n, h, w, _ = field.shape
+    assert field_ids.dtype == torch.int64 and field_ids.is_contiguous() and field_ids.numel() == n
+    taps = [int(t) for t in taps]
+    assert len(taps) % 2 == 1
+    t = (c_int32 * len(taps))(*taps)
+    _check(load_library().dfd_elastic_field(_ptr(field), n, h, w, _ptr(field_ids), int(seed) & 0xFFFFFFFFFFFFFFFF, t, len(taps) // 2,
+                                            int(alpha_q), _stream()), "dfd_elastic_field")
+    return field
+
+
+def elastic_remap_u8(clips, out, field, field_of_clip):
+    """out[b] = clips[b] warped by field[field_of_clip[b]], every frame and channel alike (include/dfdclip_elastic.h); clips,
+    out u8 [B,T,3,H,W] (distinct), field i16 [n,H,W,2] as `elastic_field` wrote it, field_of_clip i32 [B] on the device; an
+    index outside [0, n) copies the clip."""
+    _dev(clips, out, field, field_of_clip)
+    assert clips.dtype == torch.uint8 and out.dtype == torch.uint8 and clips.dim() == 5 and clips.shape[2] == 3
+    assert clips.is_contiguous() and out.is_contiguous() and out.shape == clips.shape
+    B, T, _, h, w = clips.shape
+    assert field.dtype == torch.int16 and field.is_contiguous() and field.dim() == 4 and tuple(field.shape[1:]) == (h, w, 2)
+    assert field_of_clip.dtype == torch.int32 and field_of_clip.is_contiguous() and field_of_clip.numel() == B
+    _check(load_library().dfd_elastic_remap_u8(_ptr(clips), _ptr(out), B, T, h, w, _ptr(field) if field.shape[0] else c_void_p(0),
+                                               field.shape[0], _ptr(field_of_clip), _stream()), "dfd_elastic_remap_u8")
     return out
 
 

@@ -7,7 +7,8 @@ code, so that a reference user finds the same step semantics on top of `Detector
                   set: forward(train=True, single_task=idx) -> backward(task_loss[idx].mean() + Σ other)
                   -> [gradient all-reduce] -> optimizer.step -> lr_scheduler.step.  `augment=`: the datasets'
                   colour / JPEG / flip augmentation (`src/datasets.py:288-399`) applied to each batch's uint8 device
-                  clips first (`augment.ClipAugment`).
+                  clips first (`augment.ClipAugment`); `ssl_fake=`: the self-supervised fakes (`:401-418`, `:667-669`)
+                  made from the batch's real clips after that (`elastic.SslFake`).
   make_one_cycle  the OneCycleLR the trainer builds (`src/trainer.py:51-60`): initial lr = max/25 and
                   `total_steps = max_steps * num_processes` because Accelerate steps a prepared
                   scheduler once per process per optimizer step; `step_scheduler` mirrors that.
@@ -84,13 +85,24 @@ def _augmented(frames, augment):
     return augment(frames)
 
 
-def train_step(model, optimizer, batches, scheduler=None, total_tasks=None, teacher=None, augment=None):
+def _ssl_faked(frames, labels, ssl_fake):
+    """The batch through `ssl_fake` (an `elastic.SslFake`): (frames, labels) with the chosen real clips warped and relabelled;
+    uint8 device clips only, as for `augment`."""
+    if not (torch.is_tensor(frames) and frames.is_cuda and frames.dtype == torch.uint8):
+        raise TypeError("ssl_fake= needs uint8 device frames [B,T,3,H,W]; got "
+                        f"{getattr(frames, 'dtype', type(frames))} on {getattr(frames, 'device', 'the host')}")
+    return ssl_fake(frames, labels)
+
+
+def train_step(model, optimizer, batches, scheduler=None, total_tasks=None, teacher=None, augment=None, ssl_fake=None):
     """One optimizer step over `batches`: list of (frames, labels, mask, comps, speed, task_index)
     — one entry per training set, as the reference draws one batch per set per step.
     With an `EmaTeacher` that has started teaching, every task contributes a loss (the other tasks
     against the teacher's soft labels); the teacher is updated after the optimizer step.
     `augment`: an `augment.ClipAugment`; each batch's uint8 device frames go through it (one fresh draw per batch) before
     the model and the teacher see them, as the reference's datasets augment before collation.
+    `ssl_fake`: an `elastic.SslFake`; after `augment` (the reference's order, `src/datasets.py:665-668`) each batch's real
+    clips whose coin fired are warped elastically and labelled fake, on the device and without a sync.
     Returns {"losses": [...per batch mean task loss...], "logits": [...]}."""
     total_tasks = total_tasks or len(model.out_dim)
     model.zero_grad()
@@ -100,6 +112,8 @@ def train_step(model, optimizer, batches, scheduler=None, total_tasks=None, teac
     for frames, labels, mask, comps, speed, task_index in batches:
         if augment is not None:
             frames = _augmented(frames, augment)
+        if ssl_fake is not None:
+            frames, labels = _ssl_faked(frames, labels, ssl_fake)
         if teaching:
             y_list = teacher.labels(frames, mask, labels, task_index, total_tasks)
         else:
