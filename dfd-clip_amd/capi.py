@@ -196,8 +196,15 @@ ELASTIC_SIGNATURES = {
 }
 
 # test / measurement hooks outside the ABI header (include/dfdclip_hooks.h)
+class AttentionPlan(Structure):
+    """dfd_attention_plan_t (include/dfdclip_hooks.h)."""
+    _fields_ = [("path", c_int32), ("grid", c_uint32), ("block", c_uint32), ("chunk", c_int32), ("lds", c_uint64)]
+
+
 HOOK_SIGNATURES = {
     "dfd_attention_set_variant": (c_int, [c_int]),
+    "dfd_attention_last_path": (c_int, []),
+    "dfd_attention_plan": (c_int, [c_int, c_int, c_int, c_int, c_int64, c_int64, c_int, POINTER(AttentionPlan)]),
     "dfd_gemm_pair_set_variant": (c_int, [c_int]),
     "dfd_gemm_pair_plan": (c_int, [c_int64, c_int, c_int]),
     "dfd_gemm_pair_launches": (c_int64, []),
@@ -205,6 +212,10 @@ HOOK_SIGNATURES = {
     "dfd_stream_policy_set": (c_uint, [c_uint]),
     "dfd_stream_policy_get": (c_uint, []),
 }
+
+# kernels behind dfd_attention_fwd (DFD_ATTN_* of include/dfdclip_hooks.h, which holds the selection table)
+(ATTN_ROWS, ATTN_ROWS_CHUNKED, ATTN_ITEM7, ATTN_ITEM9, ATTN_PERSIST7_SHORT, ATTN_PERSIST7, ATTN_XROW,
+ ATTN_STREAM) = range(1, 9)
 
 # families of dfd_stream_policy_set (include/dfdclip_hooks.h)
 STREAM_DECODER_KV, STREAM_DECODER_WEIGHTS, STREAM_OPTIMIZER, STREAM_ENCODER_ROWS, STREAM_ALL = 1, 2, 4, 8, 15
@@ -613,6 +624,24 @@ def attention_set_variant(variant):
     form); 2 = skip the streaming bf16 MFMA kernel, so the rows kernel serves what it served before.  Per thread.  Returns
     the previous value."""
     return load_library().dfd_attention_set_variant(int(variant))
+
+
+def attention_last_path():
+    """ATTN_* of the kernel that served this thread's last successful attention_fwd, 0 before any."""
+    return load_library().dfd_attention_last_path()
+
+
+def attention_plan(dtype, n_frames, tokens, heads, ld_qkv=None, ld_out=None, n_cu=256):
+    """What attention_fwd would launch for this shape under the thread's variant: an AttentionPlan (path, grid, block,
+    chunk, lds).  Dense rows unless ld_qkv / ld_out (elements) are given; n_cu <= 0 asks the current device.  Raises
+    DfdError for a shape attention_fwd refuses.  Touches no device with n_cu > 0."""
+    D = heads * 64
+    plan = AttentionPlan()
+    rc = load_library().dfd_attention_plan(_DTYPE[dtype], n_frames, tokens, heads, 3 * D if ld_qkv is None else ld_qkv,
+                                           D if ld_out is None else ld_out, n_cu, ctypes.byref(plan))
+    if rc < 0:
+        raise DfdError(f"dfd_attention_plan failed ({rc}): {load_library().dfd_last_error().decode()}")
+    return plan
 
 
 def attention_fwd(qkv, out, n_frames, tokens, heads, head_dim=64):

@@ -9,14 +9,12 @@
 // attn_rows_chunked_kernel: the same arithmetic in the same order per query (attn_row_key), with K and V staged in
 //   key chunks inside the key loop, for token counts whose whole K and V do not fit the 160 KiB of LDS (f32 above 320
 //   tokens, bf16 above 640).  Bit-identical to the whole-head form wherever both can run.
-// The bf16 MFMA kernels live in attention_mfma.hip (193..224 and 257..288 tokens) and attention_mfma_any.hip (the rest
-// from 33 tokens up).
-#include "common.hpp"
-#include "../../include/dfdclip_hooks.h"
+// The bf16 MFMA kernels live in attention_mfma.hip, attention_mfma_xrow.hip and attention_mfma_any.hip; which kernel serves
+// a call is decided in one place, attn_plan (attention_common.hpp; the table is in include/dfdclip_hooks.h).
+// dfd_attention_fwd here validates, plans, hands the call to the planned kernel's file and records the path.
+#include "attention_common.hpp"
 
 namespace {
-
-constexpr int HD = 64;
 
 template <typename T> struct Vec16;  // 16-byte vector of T
 template <> struct Vec16<float> { using type = f32x4; static constexpr int N = 4; };
@@ -160,62 +158,66 @@ __global__ __launch_bounds__(256) void attn_rows_chunked_kernel(const T* __restr
 }
 
 template <typename T>
-void launch_rows(const void* qkv, int64_t ld_qkv, void* out, int64_t ld_out, int n_frames, int tokens, int heads, float scale,
-                 int chunk, hipStream_t st) {
-  const dim3 grid(n_frames * heads), block(256);
-  if (chunk > 0) {  // chunked staging: at most 64 KiB, two workgroups per CU
-    const size_t lds = (size_t)2 * chunk * HD * sizeof(T);
-    hipLaunchKernelGGL((attn_rows_chunked_kernel<T>), grid, block, lds, st, static_cast<const T*>(qkv), ld_qkv, static_cast<T*>(out),
-                       ld_out, tokens, heads, scale, chunk);
-    return;
-  }
-  const size_t lds = (size_t)2 * tokens * HD * sizeof(T);
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_rows_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((attn_rows_kernel<T>), grid, block, lds, st, static_cast<const T*>(qkv), ld_qkv, static_cast<T*>(out), ld_out,
-                     tokens, heads, scale);
+int launch_rows(const AttnPlan& p, const AttnCall& c) {
+  const T* qkv = static_cast<const T*>(c.qkv);
+  T* out = static_cast<T*>(c.out);
+  if (p.path == ATTN_ROWS_CHUNKED)
+    return attn_launch<&attn_rows_chunked_kernel<T>>("dfd_attention_fwd", p, c.st, qkv, c.ld_qkv, out, c.ld_out, c.tokens, c.heads, c.scale, p.chunk);
+  return attn_launch<&attn_rows_kernel<T>>("dfd_attention_fwd", p, c.st, qkv, c.ld_qkv, out, c.ld_out, c.tokens, c.heads, c.scale);
 }
 
 thread_local int g_attn_variant = 0;
+thread_local int g_attn_last_path = 0;
+
+// What dfd_attention_fwd refuses about a shape, and the plan for what it accepts.
+int checked_plan(AttnPlan* p, int dtype, int n_frames, int tokens, int heads, int64_t ld_qkv, int64_t ld_out, int n_cu) {
+  DFD_REQUIRE(n_frames >= 0 && tokens > 0 && heads > 0, "dfd_attention_fwd: bad shape");
+  DFD_REQUIRE(dtype == DFD_F32 || dtype == DFD_BF16, "dfd_attention_fwd: dtype=%d", dtype);
+  const int esz = dtype == DFD_F32 ? 4 : 2;
+  DFD_REQUIRE(ld_qkv >= 3 * heads * HD && ld_out >= heads * HD && (ld_qkv * esz) % 16 == 0 && (ld_out * esz) % 16 == 0,
+              "dfd_attention_fwd: bad leading dimensions");
+  *p = attn_plan(dtype, n_frames, tokens, heads, ld_qkv, ld_out, g_attn_variant, n_cu > 0 ? n_cu : dfd_cu_count());
+  DFD_REQUIRE(p->path != ATTN_NONE, "dfd_attention_fwd: %lld (frame, head) items do not fit a grid", (long long)n_frames * heads);
+  return DFD_OK;
+}
 
 }  // namespace
 
-// Test hook (include/dfdclip_hooks.h): 0 = default, 1 = force the chunked staging of the rows kernel with 16-key chunks,
-// 2 = skip the streaming MFMA kernel.  Per thread; returns the previous value.
+// Test hooks (include/dfdclip_hooks.h, which also holds the selection table).  Variant: 0 = default, 1 = force the chunked
+// staging of the rows kernel with 16-key chunks, 2 = skip the streaming MFMA kernel.  Per thread; returns the previous value.
 extern "C" int dfd_attention_set_variant(int variant) {
   const int old = g_attn_variant;
   g_attn_variant = variant;
   return old;
 }
 
-// MFMA kernel (attention_mfma.hip); returns 1 when the shape is not eligible
-int dfd_attention_mfma_try(const void* qkv, int64_t ld_qkv, void* out, int64_t ld_out, int n_frames, int tokens,
-                           int heads, float scale, hipStream_t st, int use_any);
+extern "C" int dfd_attention_last_path(void) { return g_attn_last_path; }
+
+extern "C" int dfd_attention_plan(int dtype, int n_frames, int tokens, int heads, int64_t ld_qkv, int64_t ld_out, int n_cu,
+                                  dfd_attention_plan_t* out) {
+  AttnPlan p;
+  if (checked_plan(&p, dtype, n_frames, tokens, heads, ld_qkv, ld_out, n_cu) != DFD_OK) return -1;
+  if (out) *out = dfd_attention_plan_t{p.path, p.grid, p.block, p.chunk, (uint64_t)p.lds};
+  return p.path;
+}
 
 extern "C" int dfd_attention_fwd(const void* qkv, int64_t ld_qkv, void* out, int64_t ld_out, int dtype, int n_frames,
                                  int tokens, int heads, int head_dim, float scale, void* stream) {
   DFD_REQUIRE(qkv && out, "dfd_attention_fwd: null pointer");
   DFD_REQUIRE(head_dim == HD, "dfd_attention_fwd: head_dim=%d, only 64 is supported", head_dim);
-  DFD_REQUIRE(n_frames >= 0 && tokens > 0 && heads > 0, "dfd_attention_fwd: bad shape");
-  DFD_REQUIRE(dtype == DFD_F32 || dtype == DFD_BF16, "dfd_attention_fwd: dtype=%d", dtype);
-  const int esz = dtype == DFD_F32 ? 4 : 2;
-  DFD_REQUIRE(ld_qkv >= 3 * heads * HD && ld_out >= heads * HD && (ld_qkv * esz) % 16 == 0 && (ld_out * esz) % 16 == 0,
-              "dfd_attention_fwd: bad leading dimensions");
+  AttnPlan p;
+  if (int rc = checked_plan(&p, dtype, n_frames, tokens, heads, ld_qkv, ld_out, 0)) return rc;
   DFD_REQUIRE(dfd_aligned16(qkv) && dfd_aligned16(out), "dfd_attention_fwd: pointers must be 16-byte aligned");
   if (n_frames == 0) return DFD_OK;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int variant = g_attn_variant;
-  if (dtype == DFD_BF16) {
-    const int rc = dfd_attention_mfma_try(qkv, ld_qkv, out, ld_out, n_frames, tokens, heads, scale, st, variant != 2);
-    if (rc <= 0) return rc;
+  const AttnCall c{qkv, ld_qkv, out, ld_out, n_frames, tokens, heads, scale, static_cast<hipStream_t>(stream)};
+  int rc;
+  switch (p.path) {
+    case ATTN_ROWS:
+    case ATTN_ROWS_CHUNKED: rc = dtype == DFD_F32 ? launch_rows<float>(p, c) : launch_rows<bf16_t>(p, c); break;
+    case ATTN_XROW: rc = dfd_attn_launch_xrow(p, c); break;
+    case ATTN_STREAM: rc = dfd_attn_launch_stream(p, c); break;
+    default: rc = dfd_attn_launch_mfma(p, c); break;  // ATTN_ITEM7, ATTN_ITEM9, ATTN_PERSIST7_SHORT, ATTN_PERSIST7
   }
-  // whole-head staging wherever K and V of a head fit the 160 KiB of LDS; beyond that, chunks of 64 KiB
-  const size_t lds = (size_t)2 * tokens * HD * esz;
-  const int chunk = variant == 1 ? 16 : lds > 160 * 1024 ? 64 * 1024 / (2 * HD * esz) : 0;
-  if (dtype == DFD_F32)
-    launch_rows<float>(qkv, ld_qkv, out, ld_out, n_frames, tokens, heads, scale, chunk, st);
-  else
-    launch_rows<bf16_t>(qkv, ld_qkv, out, ld_out, n_frames, tokens, heads, scale, chunk, st);
-  DFD_CHECK_LAUNCH("dfd_attention_fwd");
-  return DFD_OK;
+  if (rc == DFD_OK) g_attn_last_path = p.path;
+  return rc;
 }

@@ -1,8 +1,11 @@
 // Pieces shared by the persistent encoder-attention kernels (attention_mfma.hip: 193..224 tokens, loader wave;
 // attention_mfma_xrow.hip: 257 tokens, eight query blocks + one extra row): LDS images and their LDS-DMA staging, the
 // register softmax and the second product.  head_dim 64 everywhere (reference clip/model.py:188-195).
+// At the end, the host side of the whole family behind dfd_attention_fwd: which kernel serves a call (attn_plan), the one
+// launcher, and the launch functions its four files export.
 #pragma once
 #include "common.hpp"
+#include "../../include/dfdclip_hooks.h"
 
 namespace {
 
@@ -169,3 +172,84 @@ __device__ __forceinline__ void attn_store_line(v4i_t d, __amdgpu_buffer_rsrc_t 
 template <int N> __device__ __forceinline__ void attn_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 }  // namespace
+
+// ---- host: one launch plan for the five kernels behind dfd_attention_fwd ------------------------------------------------
+// attn_plan is the only place that knows token windows, item thresholds, LDS budgets and 32-bit extents; its table is
+// written out once, in include/dfdclip_hooks.h.  A new kernel or window is a path there, a row here, a case in its
+// file's launcher and a row of the table in tests/test_abi_cpu.py.
+enum AttnPath {  // 0: no call yet / no kernel
+  ATTN_NONE = 0, ATTN_ROWS = DFD_ATTN_ROWS, ATTN_ROWS_CHUNKED = DFD_ATTN_ROWS_CHUNKED, ATTN_ITEM7 = DFD_ATTN_ITEM7,
+  ATTN_ITEM9 = DFD_ATTN_ITEM9, ATTN_PERSIST7_SHORT = DFD_ATTN_PERSIST7_SHORT, ATTN_PERSIST7 = DFD_ATTN_PERSIST7,
+  ATTN_XROW = DFD_ATTN_XROW, ATTN_STREAM = DFD_ATTN_STREAM
+};
+
+struct AttnPlan {
+  int path;  // ATTN_NONE: the (frame, head) items do not fit the grid of the kernel that would serve the call
+  unsigned grid, block;
+  size_t lds;                     // dynamic LDS of the launch
+  int chunk;                      // keys per staging chunk (ATTN_ROWS_CHUNKED), else 0
+  uint32_t qkv_bytes, out_bytes;  // what the persistent kernels' buffer descriptors span, else 0
+};
+
+constexpr size_t ATTN_LDS_MAX = 160 * 1024;  // of a CU; a launch gets 64 KiB unasked
+// LDS of the MFMA kernels (the per-item and the 257-token file assert that these are their layouts)
+constexpr size_t attn_item_lds(int nb) { return (size_t)nb * 32 * 128 + 64 * ((size_t)nb * 64 + 8); }  // K rows, transposed V
+constexpr size_t attn_persist_lds(int tokens, int nb) { return (size_t)4 * tokens * 128 + (size_t)2 * nb * 4096; }  // [K0][V0][K1][V1], 2 Q images per wave
+constexpr size_t ATTN_XROW_LDS = 4 * 257 * 128 + 8 * 2048 + 2560;
+constexpr int ATTN_STREAM_SPAN = 128;  // queries per workgroup of the streaming kernel
+
+// variant: dfd_attention_set_variant; n_cu <= 0 (the device cannot be queried) reads as 256.  No HIP call, no pointer.
+inline AttnPlan attn_plan(int dtype, int n_frames, int tokens, int heads, int64_t ld_qkv, int64_t ld_out, int variant, int n_cu) {
+  const int64_t items = (int64_t)n_frames * heads, GRID_MAX = 0x7fffffff, EXTENT_MAX = 0xfffffff0;
+  const size_t esz = dtype == DFD_F32 ? 4 : 2;
+  auto per_item = [&](int path, size_t lds, int chunk) {  // one 256-thread workgroup per item
+    return AttnPlan{items <= GRID_MAX ? path : ATTN_NONE, (unsigned)items, 256u, lds, chunk, 0u, 0u};
+  };
+  const int nb = (tokens + 31) / 32;  // the register kernels mask only their last key block: NB = ceil(tokens / 32) exactly
+  if (dtype == DFD_BF16 && (nb == 7 || nb == 9)) {
+    // persistent forms: enough items to fill the chip, a whole number of workgroups per XCD, offsets that fit 32 bits
+    const int64_t last_row = (int64_t)n_frames * tokens - 1;
+    const int64_t qkv_bytes = last_row * ld_qkv * 2 + (int64_t)3 * heads * 128, out_bytes = last_row * ld_out * 2 + (int64_t)heads * 128;
+    const unsigned grid = (unsigned)(n_cu <= 0 ? 256 : n_cu) & ~7u;
+    const size_t lds = nb == 7 ? attn_persist_lds(tokens, 7) : ATTN_XROW_LDS;
+    if (items >= 512 && grid >= 8 && qkv_bytes <= EXTENT_MAX && out_bytes <= EXTENT_MAX && (nb == 7 ? lds <= ATTN_LDS_MAX : tokens == 257))
+      return AttnPlan{nb == 9 ? ATTN_XROW : tokens <= 6 * 32 + 8 ? ATTN_PERSIST7_SHORT : ATTN_PERSIST7, grid, 512u, lds, 0,
+                      (uint32_t)qkv_bytes, (uint32_t)out_bytes};
+    return per_item(nb == 7 ? ATTN_ITEM7 : ATTN_ITEM9, attn_item_lds(nb), 0);
+  }
+  const int64_t spans = (tokens + ATTN_STREAM_SPAN - 1) / ATTN_STREAM_SPAN;
+  if (dtype == DFD_BF16 && tokens > 32 && variant != 2 && items <= GRID_MAX / spans)
+    return AttnPlan{ATTN_STREAM, (unsigned)(items * spans), 256u, 0, 0, 0u, 0u};
+  // rows: whole-head staging wherever K and V of a head fit LDS; beyond that, chunks of 64 KiB (two workgroups per CU)
+  const size_t whole = 2 * (size_t)tokens * 64 * esz;
+  const int chunk = variant == 1 ? 16 : whole > ATTN_LDS_MAX ? (int)(64 * 1024 / (2 * 64 * esz)) : 0;
+  return chunk > 0 ? per_item(ATTN_ROWS_CHUNKED, 2 * (size_t)chunk * 64 * esz, chunk) : per_item(ATTN_ROWS, whole, 0);
+}
+
+// Raise the kernel's dynamic-LDS limit the first time a launch of this instantiation asks for more than 64 KiB (once per
+// process, to the CU's whole LDS: these kernels are launched 12-24 times per pass inside graph capture), launch, report.
+template <auto Kernel, typename... A>
+int attn_launch(const char* what, const AttnPlan& p, hipStream_t st, A... args) {
+  static bool raised = false;
+  if (p.lds > 64 * 1024 && !raised) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATTN_LDS_MAX);
+    raised = true;
+  }
+  hipLaunchKernelGGL(Kernel, dim3(p.grid), dim3(p.block), p.lds, st, args...);
+  DFD_CHECK_LAUNCH(what);
+  return DFD_OK;
+}
+
+// What dfd_attention_fwd hands to the file that holds the planned kernel.  Each file exports one launcher; none decides.
+struct AttnCall {
+  const void* qkv;
+  int64_t ld_qkv;
+  void* out;
+  int64_t ld_out;
+  int n_frames, tokens, heads;
+  float scale;
+  hipStream_t st;
+};
+int dfd_attn_launch_mfma(const AttnPlan& p, const AttnCall& c);    // attention_mfma.hip: ITEM7, ITEM9, PERSIST7_SHORT, PERSIST7
+int dfd_attn_launch_xrow(const AttnPlan& p, const AttnCall& c);    // attention_mfma_xrow.hip: XROW
+int dfd_attn_launch_stream(const AttnPlan& p, const AttnCall& c);  // attention_mfma_any.hip: STREAM

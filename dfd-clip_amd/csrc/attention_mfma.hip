@@ -469,84 +469,29 @@ __global__ __launch_bounds__(512) void attn_mfma_persist_kernel(const bf16_t* __
   }
 }
 
-// 1 = not served (shape outside the persistent kernel's LDS budget or 32-bit offsets)
-template <int NB, bool SHORT>
-int launch_persist(const void* qkv, int64_t ld_qkv, void* out, int64_t ld_out, int n_frames, int tokens, int heads, float scale,
-                   hipStream_t st) {
-  const int64_t lds = (int64_t)4 * tokens * 128 + 2 * NB * 4096;
-  const int64_t qkv_bytes = ((int64_t)n_frames * tokens - 1) * ld_qkv * 2 + (int64_t)3 * heads * HD * 2;
-  const int64_t out_bytes = ((int64_t)n_frames * tokens - 1) * ld_out * 2 + (int64_t)heads * HD * 2;
-  if (lds > 160 * 1024 || qkv_bytes > (int64_t)0xfffffff0 || out_bytes > (int64_t)0xfffffff0 || (ld_qkv % 8) != 0 || (ld_out % 8) != 0) return 1;
-  static int ncu = 0;
-  if (ncu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
-    if (ncu <= 0) ncu = 256;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_mfma_persist_kernel<NB, SHORT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
-  const int grid = ncu & ~7;  // a whole number of workgroups per XCD
-  if (grid < 8) return 1;
-  hipLaunchKernelGGL((attn_mfma_persist_kernel<NB, SHORT>), dim3(grid), dim3(512), (size_t)lds, st, static_cast<const bf16_t*>(qkv),
-                     (uint32_t)(ld_qkv * 2), static_cast<bf16_t*>(out), (uint32_t)(ld_out * 2), tokens, heads, n_frames,
-                     (uint32_t)qkv_bytes, (uint32_t)out_bytes, scale * 1.4426950408889634f);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    dfd_set_error("dfd_attention_fwd(mfma, persistent): launch failed: %s", hipGetErrorString(e));
-    return DFD_ERR_LAUNCH;
-  }
-  return DFD_OK;
+template <int NB>
+int launch_item(const AttnPlan& p, const AttnCall& c) {
+  static_assert(Lds<NB>::BYTES == attn_item_lds(NB), "the plan's LDS size is the kernel's layout");
+  static_assert(Lds<NB>::VSTRIDE % 16 == 8, "Vt row stride must be 8 mod 16 bytes");
+  return attn_launch<&attn_mfma_kernel<NB>>("dfd_attention_fwd(mfma)", p, c.st, static_cast<const bf16_t*>(c.qkv), c.ld_qkv,
+                                            static_cast<bf16_t*>(c.out), c.ld_out, c.tokens, c.heads, c.scale * 1.4426950408889634f);
 }
 
-template <int NB>
-int launch(const void* qkv, int64_t ld_qkv, void* out, int64_t ld_out, int n_frames, int tokens, int heads, float scale,
-           hipStream_t st) {
-  using L = Lds<NB>;
-  static_assert(L::VSTRIDE % 16 == 8, "Vt row stride must be 8 mod 16 bytes");
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_mfma_kernel<NB>), hipFuncAttributeMaxDynamicSharedMemorySize, L::BYTES);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((attn_mfma_kernel<NB>), dim3(n_frames * heads), dim3(256), L::BYTES, st,
-                     static_cast<const bf16_t*>(qkv), ld_qkv, static_cast<bf16_t*>(out), ld_out, tokens, heads,
-                     scale * 1.4426950408889634f);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    dfd_set_error("dfd_attention_fwd(mfma): launch failed: %s", hipGetErrorString(e));
-    return DFD_ERR_LAUNCH;
-  }
-  return DFD_OK;
+template <bool SHORT>
+int launch_persist(const AttnPlan& p, const AttnCall& c) {
+  return attn_launch<&attn_mfma_persist_kernel<7, SHORT>>("dfd_attention_fwd(mfma, persistent)", p, c.st, static_cast<const bf16_t*>(c.qkv),
+                                                          (uint32_t)(c.ld_qkv * 2), static_cast<bf16_t*>(c.out), (uint32_t)(c.ld_out * 2),
+                                                          c.tokens, c.heads, c.n_frames, p.qkv_bytes, p.out_bytes,
+                                                          c.scale * 1.4426950408889634f);
 }
 
 }  // namespace
 
-
-int dfd_attention_mfma_xrow_try(const void* qkv, int64_t ld_qkv, void* out, int64_t ld_out, int n_frames, int tokens, int heads,
-                                float scale, hipStream_t st);  // attention_mfma_xrow.hip
-
-int dfd_attention_mfma_any_try(const void* qkv, int64_t ld_qkv, void* out, int64_t ld_out, int n_frames, int tokens, int heads,
-                               float scale, hipStream_t st);  // attention_mfma_any.hip
-
-// use_any = 0: token counts outside the two windows are not served (dfd_attention_set_variant(2))
-int dfd_attention_mfma_try(const void* qkv, int64_t ld_qkv, void* out, int64_t ld_out, int n_frames, int tokens, int heads,
-                           float scale, hipStream_t st, int use_any) {
-  if ((ld_qkv % 8) != 0 || (ld_out % 4) != 0) return 1;
-  // NB = ceil(tokens / 32) exactly: the kernels mask only their last key block
-  if (tokens > 6 * 32 && tokens <= 7 * 32) {
-    if (n_frames * heads >= 512) {
-      const int rc = tokens <= 6 * 32 + 8 ? launch_persist<7, true>(qkv, ld_qkv, out, ld_out, n_frames, tokens, heads, scale, st)
-                                          : launch_persist<7, false>(qkv, ld_qkv, out, ld_out, n_frames, tokens, heads, scale, st);
-      if (rc <= 0) return rc;
-    }
-    return launch<7>(qkv, ld_qkv, out, ld_out, n_frames, tokens, heads, scale, st);
+int dfd_attn_launch_mfma(const AttnPlan& p, const AttnCall& c) {
+  switch (p.path) {
+    case ATTN_PERSIST7_SHORT: return launch_persist<true>(p, c);
+    case ATTN_PERSIST7: return launch_persist<false>(p, c);
+    case ATTN_ITEM7: return launch_item<7>(p, c);
+    default: return launch_item<9>(p, c);  // ATTN_ITEM9
   }
-  if (tokens > 8 * 32 && tokens <= 9 * 32) {
-    const int rc = dfd_attention_mfma_xrow_try(qkv, ld_qkv, out, ld_out, n_frames, tokens, heads, scale, st);  // 257 tokens, >= 512 items
-    if (rc <= 0) return rc;
-    return launch<9>(qkv, ld_qkv, out, ld_out, n_frames, tokens, heads, scale, st);
-  }
-  // every other count from 33 up: the streaming kernel (32 and fewer stay on the rows kernel)
-  if (use_any && tokens > 32) return dfd_attention_mfma_any_try(qkv, ld_qkv, out, ld_out, n_frames, tokens, heads, scale, st);
-  return 1;
 }

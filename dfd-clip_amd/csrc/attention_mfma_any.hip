@@ -199,19 +199,9 @@ __global__ __launch_bounds__(256, 2) void attn_mfma_any_kernel(const bf16_t* __r
 
 }  // namespace
 
-// 1 = not served (fewer than 33 tokens, or a grid past 2^31 - 1 workgroups)
-int dfd_attention_mfma_any_try(const void* qkv, int64_t ld_qkv, void* out, int64_t ld_out, int n_frames, int tokens, int heads,
-                               float scale, hipStream_t st) {
-  if (tokens < 33 || (ld_qkv % 8) != 0 || (ld_out % 4) != 0) return 1;
-  const int spans = (tokens + ANY_SPAN - 1) / ANY_SPAN;
-  const int64_t grid = (int64_t)n_frames * heads * spans;
-  if (grid > (int64_t)0x7fffffff) return 1;
-  hipLaunchKernelGGL(attn_mfma_any_kernel, dim3((unsigned)grid), dim3(256), 0, st, static_cast<const bf16_t*>(qkv), ld_qkv,
-                     static_cast<bf16_t*>(out), ld_out, tokens, heads, spans, scale * 1.4426950408889634f);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    dfd_set_error("dfd_attention_fwd(mfma, streaming): launch failed: %s", hipGetErrorString(e));
-    return DFD_ERR_LAUNCH;
-  }
-  return DFD_OK;
+int dfd_attn_launch_stream(const AttnPlan& p, const AttnCall& c) {
+  static_assert(ANY_SPAN == ATTN_STREAM_SPAN, "the plan's grid counts the kernel's spans");
+  const int spans = (c.tokens + ANY_SPAN - 1) / ANY_SPAN;
+  return attn_launch<&attn_mfma_any_kernel>("dfd_attention_fwd(mfma, streaming)", p, c.st, static_cast<const bf16_t*>(c.qkv), c.ld_qkv,
+                                            static_cast<bf16_t*>(c.out), c.ld_out, c.tokens, c.heads, spans, c.scale * 1.4426950408889634f);
 }

@@ -332,30 +332,9 @@ __global__ __launch_bounds__(512) void attn_mfma_xrow_kernel(const bf16_t* __res
 
 }  // namespace
 
-// 1 = not served (another token count, too few items to fill the chip, or 32-bit offsets do not reach)
-int dfd_attention_mfma_xrow_try(const void* qkv, int64_t ld_qkv, void* out, int64_t ld_out, int n_frames, int tokens, int heads,
-                                float scale, hipStream_t st) {
-  if (tokens != XTOKENS || n_frames * heads < 512) return 1;
-  const int64_t qkv_bytes = ((int64_t)n_frames * tokens - 1) * ld_qkv * 2 + (int64_t)3 * heads * HD * 2;
-  const int64_t out_bytes = ((int64_t)n_frames * tokens - 1) * ld_out * 2 + (int64_t)heads * HD * 2;
-  if (qkv_bytes > (int64_t)0xfffffff0 || out_bytes > (int64_t)0xfffffff0 || (ld_qkv % 8) != 0 || (ld_out % 8) != 0) return 1;
-  static int ncu = 0;
-  if (ncu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
-    if (ncu <= 0) ncu = 256;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_mfma_xrow_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
-  const int grid = ncu & ~7;  // a whole number of workgroups per XCD
-  if (grid < 8) return 1;
-  hipLaunchKernelGGL(attn_mfma_xrow_kernel, dim3(grid), dim3(512), (size_t)XROW_LDS, st, static_cast<const bf16_t*>(qkv),
-                     (uint32_t)(ld_qkv * 2), static_cast<bf16_t*>(out), (uint32_t)(ld_out * 2), heads, n_frames,
-                     (uint32_t)qkv_bytes, (uint32_t)out_bytes, scale * 1.4426950408889634f);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    dfd_set_error("dfd_attention_fwd(mfma, 257 tokens): launch failed: %s", hipGetErrorString(e));
-    return DFD_ERR_LAUNCH;
-  }
-  return DFD_OK;
+int dfd_attn_launch_xrow(const AttnPlan& p, const AttnCall& c) {
+  static_assert(XROW_LDS == ATTN_XROW_LDS, "the plan's LDS size is the kernel's layout");
+  return attn_launch<&attn_mfma_xrow_kernel>("dfd_attention_fwd(mfma, 257 tokens)", p, c.st, static_cast<const bf16_t*>(c.qkv),
+                                             (uint32_t)(c.ld_qkv * 2), static_cast<bf16_t*>(c.out), (uint32_t)(c.ld_out * 2), c.heads,
+                                             c.n_frames, p.qkv_bytes, p.out_bytes, c.scale * 1.4426950408889634f);
 }

@@ -38,6 +38,18 @@ void dfd_set_error(const char* fmt, ...);
 
 static inline bool dfd_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// Compute units of the current device, queried once per process (0: the device cannot be queried; the next call asks
+// again).  One process drives one GPU (launch.py), so the first answer holds for the life of the process.
+inline int dfd_cu_count() {
+  static int n_cu = 0;
+  if (n_cu == 0) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
+  }
+  return n_cu;
+}
+
 // ---- device helpers --------------------------------------------------------------------
 __device__ __forceinline__ float to_f32(float v) { return v; }
 __device__ __forceinline__ float to_f32(bf16_t v) { return (float)v; }

@@ -15,17 +15,6 @@ typedef int v4i_t __attribute__((ext_vector_type(4)));
 typedef v4i_t v4i;
 typedef int v8i __attribute__((ext_vector_type(8)));
 
-// compute units of the device, queried once per process (0: the device cannot be queried)
-inline int persistent_cu_count() {
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
-  }
-  return n_cu;
-}
-
 namespace {
 
 // Output stores: non-temporal (aux bit 1) when the caller marks the output as streaming: it then goes past L2
@@ -387,7 +376,7 @@ struct TilePlan {
 // spare_if_free: `spare_cus` is a request, not an order — honoured where the rounds of tiles (at the best height allowed)
 // stay the same.  force224: the epilogue only exists for 224-row tiles.
 inline TilePlan plan_tiles(int64_t M, int N, int spare_cus, bool spare_if_free, int tile_rows, bool f8, bool force224) {
-  const int n_cu = persistent_cu_count(), tiles_n = N / TN;
+  const int n_cu = dfd_cu_count(), tiles_n = N / TN;
   if (n_cu == 0) return TilePlan{0, 0, 0, 0};
   int cus = n_cu - spare_cus;
   cus = cus < n_cu / 2 ? n_cu / 2 : cus;

@@ -10,11 +10,56 @@
 extern "C" {
 #endif
 
-/* Which kernel dfd_attention_fwd picks.  0 (default) = as documented in dfdclip.h; 1 = the rows kernel (f32, and bf16
- * where no MFMA kernel serves the shape) stages K and V in chunks of 16 keys whatever the token count — the form it
- * otherwise takes only where K and V of a head exceed 160 KiB of LDS, bit-identical to the whole-head form; 2 = skip
- * the streaming bf16 MFMA kernel (attention_mfma_any.hip), so that the rows kernel serves the token counts outside the
- * 193..224 and 257..288 windows as it did before that kernel existed.  Per thread; returns the previous value. */
+/* The kernels behind dfd_attention_fwd and the rule that picks one (attn_plan in csrc/attention_common.hpp is the only
+ * code that knows it).  items = n_frames * heads, esz = bytes per element, n_cu = compute units of the device (256 where
+ * it cannot be queried), the two extents are the bytes a persistent kernel addresses with 32-bit offsets:
+ *   qkv_bytes = (n_frames*tokens - 1) * ld_qkv * 2 + 3*heads*128,   out_bytes = (n_frames*tokens - 1) * ld_out * 2 + heads*128.
+ * The first row that matches wins; bf16 unless it says f32:
+ *   f32, or tokens <= 32                                                          -> rows (below)
+ *   193..224 tokens, items >= 512, tokens <= 208, both extents <= 0xfffffff0,
+ *     (n_cu & ~7) >= 8                                   -> PERSIST7_SHORT (tokens <= 200) or PERSIST7:
+ *                                                           grid n_cu & ~7, block 512, LDS 512*tokens + 57,344
+ *   193..224 tokens otherwise                            -> ITEM7: grid items, block 256, LDS 57,856
+ *   257 tokens, items >= 512, both extents fit, (n_cu & ~7) >= 8
+ *                                                        -> XROW: grid n_cu & ~7, block 512, LDS 150,528
+ *   257..288 tokens otherwise                            -> ITEM9: grid items, block 256, LDS 74,240
+ *   33 tokens and up, variant != 2, items * ceil(tokens / 128) <= 2^31 - 1
+ *                                                        -> STREAM: that grid, block 256, no dynamic LDS
+ *   everything else                                      -> rows
+ * rows: grid items, block 256; chunk = 16 keys under variant 1, else 65,536 / (128*esz) keys where K and V of a head
+ * (2*tokens*64*esz bytes) exceed 160 KiB (f32 above 320 tokens, bf16 above 640), else 0.  chunk > 0 -> ROWS_CHUNKED with
+ * LDS 2*chunk*64*esz, else ROWS with LDS 2*tokens*64*esz.  A call whose items exceed 2^31 - 1 on a path whose grid is
+ * `items` (rows, ITEM7, ITEM9) is refused. */
+enum {
+  DFD_ATTN_ROWS = 1,           /* attention.hip: K and V of a head in LDS, one query row per thread */
+  DFD_ATTN_ROWS_CHUNKED = 2,   /* attention.hip: the same arithmetic, K and V staged in key chunks */
+  DFD_ATTN_ITEM7 = 3,          /* attention_mfma.hip: one workgroup per item, 7 key blocks */
+  DFD_ATTN_ITEM9 = 4,          /* attention_mfma.hip: one workgroup per item, 9 key blocks */
+  DFD_ATTN_PERSIST7_SHORT = 5, /* attention_mfma.hip: persistent, at most 8 keys in the last block */
+  DFD_ATTN_PERSIST7 = 6,       /* attention_mfma.hip: persistent */
+  DFD_ATTN_XROW = 7,           /* attention_mfma_xrow.hip: persistent, 257 tokens */
+  DFD_ATTN_STREAM = 8          /* attention_mfma_any.hip: streaming, any token count */
+};
+typedef struct {
+  int32_t path;         /* DFD_ATTN_* */
+  uint32_t grid, block; /* workgroups and threads per workgroup */
+  int32_t chunk;        /* keys per staging chunk of DFD_ATTN_ROWS_CHUNKED, else 0 */
+  uint64_t lds;         /* dynamic LDS bytes of the launch */
+} dfd_attention_plan_t;
+
+/* The path (DFD_ATTN_*) of this thread's last successful dfd_attention_fwd that launched a kernel; 0 = no call yet. */
+int dfd_attention_last_path(void);
+/* What dfd_attention_fwd would do with this shape under the thread's current variant: returns the path and fills *out
+ * (may be NULL), or returns -1 with dfd_last_error() for what dfd_attention_fwd refuses.  No pointer is involved and,
+ * with n_cu > 0, no device (n_cu <= 0: the current device's count). */
+int dfd_attention_plan(int dtype, int n_frames, int tokens, int heads, int64_t ld_qkv, int64_t ld_out, int n_cu,
+                       dfd_attention_plan_t* out);
+
+/* Changes the selection above.  0 (default) = the table; 1 = the rows kernel (f32, and bf16 where no MFMA kernel serves
+ * the shape) stages K and V in chunks of 16 keys whatever the token count — the form it otherwise takes only where K
+ * and V of a head exceed 160 KiB of LDS, bit-identical to the whole-head form; 2 = skip the streaming bf16 MFMA kernel
+ * (attention_mfma_any.hip), so that the rows kernel serves the token counts outside the 193..224 and 257..288 windows
+ * as it did before that kernel existed.  Per thread; returns the previous value. */
 int dfd_attention_set_variant(int variant);
 
 /* The c_fc -> c_proj pair of the encoder's MLP (DFD_GEMM_C_BLOCKED / DFD_GEMM_A_BLOCKED).  0 (default) = the pair keeps

@@ -63,7 +63,8 @@ def test_attention_variant_hook_is_exported_and_per_thread():
     from dfd_clip_amd import capi
     build()
     lib = capi.load_library()
-    assert "dfd_attention_set_variant" in capi.HOOK_SIGNATURES and "dfd_attention_set_variant" not in capi.SIGNATURES
+    for name in ("dfd_attention_set_variant", "dfd_attention_last_path", "dfd_attention_plan"):
+        assert name in capi.HOOK_SIGNATURES and name not in capi.SIGNATURES and hasattr(lib, name), name
     assert lib.dfd_abi_version() == capi.ABI_VERSION == 17
     assert capi.attention_set_variant(2) == 0
     seen = []
@@ -71,4 +72,15 @@ def test_attention_variant_hook_is_exported_and_per_thread():
     t.start()
     t.join()
     assert seen == [0], "another thread starts at the default"
+    # the plan hook answers under the calling thread's variant: here 2 (no streaming kernel), in a new thread the default
+    paths = [capi.attention_plan(torch.bfloat16, 2, 50, 2).path]
+    t = threading.Thread(target=lambda: paths.append(capi.attention_plan(torch.bfloat16, 2, 50, 2).path))
+    t.start()
+    t.join()
+    assert paths == [capi.ATTN_ROWS, capi.ATTN_STREAM]
     assert capi.attention_set_variant(0) == 2 and capi.attention_set_variant(0) == 0
+    # no attention call on this thread or a new one yet: the last path is per thread and starts at 0
+    t = threading.Thread(target=lambda: seen.append(capi.attention_last_path()))
+    t.start()
+    t.join()
+    assert seen == [0, 0]

@@ -56,12 +56,14 @@ def random_case(n, tokens, heads, dtype):
     return qkv, reference(qkv, n, tokens, heads)
 
 
-def run(capi, qkv, n, tokens, heads, want, tol, msg, variant=0):
+def run(capi, qkv, n, tokens, heads, want, tol, msg, path, variant=0):
+    """`path`: the kernel (capi.ATTN_*) that both the dense and the guarded call (ld + 8) must take."""
     D = heads * 64
 
     def op(b):
         out = b.out((n * tokens, D), qkv.dtype, pad=8, name="out")
         capi.attention_fwd(b.inp(qkv, pad=8, name="qkv"), out, n, tokens, heads)
+        assert capi.attention_last_path() == path, f"{msg}: {'guarded' if b.guard else 'dense'} call took kernel {capi.attention_last_path()}, not {path}"
         return {"out": out}
     capi.attention_set_variant(variant)
     try:
@@ -79,7 +81,7 @@ BF16_CASES = [(n, t, h) for t in TOKENS for h in (2, 12) for n in ((1,) if t == 
 @pytest.mark.parametrize("n,tokens,heads", BF16_CASES)
 def test_bf16_streaming_kernel(capi, n, tokens, heads):
     qkv, want = random_case(n, tokens, heads, BF16)
-    run(capi, qkv, n, tokens, heads, want, BF16_TOL, f"bf16 {n}x{tokens}x{heads}")
+    run(capi, qkv, n, tokens, heads, want, BF16_TOL, f"bf16 {n}x{tokens}x{heads}", capi.ATTN_STREAM)
 
 
 # ---- where the running maximum lands ------------------------------------------------------------------------------
@@ -124,7 +126,7 @@ def test_bf16_running_maximum(capi, kind):
     p = (s - s.amax(dim=-1, keepdim=True)).exp()
     emu = (p.to(BF16).double() @ v / p.sum(dim=-1, keepdim=True)).permute(0, 2, 1, 3).reshape(tokens, heads * 64).cpu()
     assert ((emu - want).abs() <= BF16_TOL[0] + BF16_TOL[1] * want.abs()).all()
-    run(capi, qkv, 1, tokens, heads, want, BF16_TOL, f"bf16 max {kind}")
+    run(capi, qkv, 1, tokens, heads, want, BF16_TOL, f"bf16 max {kind}", capi.ATTN_STREAM)
 
 
 # ---- launch independence ------------------------------------------------------------------------------------------
@@ -151,8 +153,8 @@ def test_bf16_whole_launch_equals_chunks_of_three_frames(capi):
 def test_f32_chunked_staging_is_bit_identical(capi, tokens):
     n, heads = 3, 2
     qkv, want = random_case(n, tokens, heads, F32)
-    whole = run(capi, qkv, n, tokens, heads, want, F32_TOL, f"f32 {tokens} whole-head")
-    chunked = run(capi, qkv, n, tokens, heads, want, F32_TOL, f"f32 {tokens} 16-key chunks", variant=1)
+    whole = run(capi, qkv, n, tokens, heads, want, F32_TOL, f"f32 {tokens} whole-head", capi.ATTN_ROWS)
+    chunked = run(capi, qkv, n, tokens, heads, want, F32_TOL, f"f32 {tokens} 16-key chunks", capi.ATTN_ROWS_CHUNKED, variant=1)
     same_bits(whole, chunked, f"f32 {tokens}: chunked and whole-head staging")
 
 
@@ -160,11 +162,11 @@ def test_f32_chunked_staging_is_bit_identical(capi, tokens):
 def test_f32_above_the_lds_ceiling(capi, n, tokens):
     heads = 2
     qkv, want = random_case(n, tokens, heads, F32)
-    run(capi, qkv, n, tokens, heads, want, F32_TOL, f"f32 {n}x{tokens}")
+    run(capi, qkv, n, tokens, heads, want, F32_TOL, f"f32 {n}x{tokens}", capi.ATTN_ROWS_CHUNKED)
 
 
 def test_bf16_fallback_above_the_lds_ceiling(capi):
     """641 tokens with the streaming kernel skipped: 164,096 B of K and V, the rows kernel's chunked form."""
     n, tokens, heads = 2, 641, 2
     qkv, want = random_case(n, tokens, heads, BF16)
-    run(capi, qkv, n, tokens, heads, want, BF16_TOL, "bf16 641 rows kernel", variant=2)
+    run(capi, qkv, n, tokens, heads, want, BF16_TOL, "bf16 641 rows kernel", capi.ATTN_ROWS_CHUNKED, variant=2)

@@ -615,7 +615,8 @@ def test_gemm_at_b(capi, R, Ma, Nb, dtype):
 @pytest.mark.parametrize("dtype,out_pad", [(F32, 8), (BF16, 8), (F32, 4)])
 def test_attention_fwd(capi, n, tokens, heads, dtype, out_pad):
     """ld_qkv = 3D + 8, ld_out = D + 8 (f32 also D + 4); the last frame's last row ends at the row padding and guard.
-    The per-item and the persistent kernels are one family (pinned bit-identical by test_hip_kernels.py)."""
+    The per-item and the persistent kernels are one family (pinned bit-identical by test_hip_kernels.py); the padded
+    rows do not change which kernel serves the call."""
     D = heads * 64
     qkv = rnd(n * tokens, 3 * D, seed=16)
     qkv[:, :D] *= 2.0
@@ -624,12 +625,17 @@ def test_attention_fwd(capi, n, tokens, heads, dtype, out_pad):
     aff = torch.einsum("nqhc,nkhc->nqkh", t[:, :, 0] / 8.0, t[:, :, 1]).softmax(dim=-2)
     want = torch.einsum("nqlh,nlhc->nqhc", aff, t[:, :, 2]).reshape(n * tokens, D)
 
+    paths = []
+
     def op(b):
         out = b.out((n * tokens, D), dtype, pad=out_pad, name="out")
         capi.attention_fwd(b.inp(qkv, pad=8, name="qkv"), out, n, tokens, heads)
+        paths.append(capi.attention_last_path())
         return {"out": out}
     tol = (2e-5, 1e-5) if dtype == F32 else (2e-2, 2 ** -7)
     verify(*both(op), {"out": (want, *tol)}, msg="attention")
+    assert len(paths) == 2 and paths[0] == paths[1] != 0, f"dense and guarded call took kernels {paths}"
+    assert paths[0] == capi.attention_plan(dtype, n, tokens, heads, n_cu=0).path
 
 
 # ---- decoder and head kernels -------------------------------------------------------------------------------------

@@ -560,8 +560,13 @@ def test_gemm_qkv_export_layout(capi, dtype):
     assert torch.equal(ke2, ke) and torch.equal(ve2, ve) and torch.equal(c3[:, D:], c[:, D:]) and (c3[:, :D] == 0).all()
 
 
-@pytest.mark.parametrize("n,tokens,heads", [(2, 5, 2), (3, 197, 4), (1, 257, 2), (2, 50, 12), (64, 197, 12), (45, 200, 12),
-                                            (43, 205, 12), (48, 210, 12), (33, 257, 16), (47, 230, 12)])
+# (n, tokens, heads) -> the kernel the bf16 call takes (capi.ATTN_*); f32 always takes the rows kernel
+ATTENTION_CASES = {(2, 5, 2): "ROWS", (3, 197, 4): "ITEM7", (1, 257, 2): "ITEM9", (2, 50, 12): "STREAM", (64, 197, 12): "PERSIST7_SHORT",
+                   (45, 200, 12): "PERSIST7_SHORT", (43, 205, 12): "PERSIST7", (48, 210, 12): "ITEM7", (33, 257, 16): "XROW",
+                   (47, 230, 12): "STREAM"}
+
+
+@pytest.mark.parametrize("n,tokens,heads", list(ATTENTION_CASES))
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_encoder_attention(capi, n, tokens, heads, dtype):
     D = heads * 64
@@ -573,30 +578,44 @@ def test_encoder_attention(capi, n, tokens, heads, dtype):
     want = torch.einsum("nqlh,nlhc->nqhc", aff, t[:, :, 2]).reshape(n * tokens, D)
     out = torch.empty(n * tokens, D, device="cuda", dtype=dtype)
     capi.attention_fwd(qkv.to(dtype).cuda(), out, n, tokens, heads)
+    path = "ROWS" if dtype == torch.float32 else ATTENTION_CASES[n, tokens, heads]
+    assert capi.attention_last_path() == getattr(capi, "ATTN_" + path)
     if dtype == torch.float32:
         assert_close(out, want, 2e-5, 1e-5, "attention f32")
     else:  # P is rounded to bf16 before the PV product in the MFMA kernel
         assert_close(out, want, 2e-2, 2 ** -7, "attention bf16")
 
 
-@pytest.mark.parametrize("n,tokens,heads", [(64, 197, 12), (45, 200, 12), (43, 205, 12), (40, 257, 16), (45, 288, 12), (50, 226, 12)])
+# (n, tokens, heads) -> (the whole launch's kernel, the kernel of its chunks of 16 frames)
+LAUNCH_CASES = {(64, 197, 12): ("PERSIST7_SHORT", "ITEM7"), (45, 200, 12): ("PERSIST7_SHORT", "ITEM7"), (43, 205, 12): ("PERSIST7", "ITEM7"),
+                (40, 257, 16): ("XROW", "ITEM9"), (45, 288, 12): ("ITEM9", "ITEM9"), (50, 226, 12): ("STREAM", "STREAM"),
+                (43, 193, 12): ("PERSIST7_SHORT", "ITEM7"), (43, 208, 12): ("PERSIST7", "ITEM7"), (32, 257, 16): ("XROW", "ITEM9")}
+
+
+@pytest.mark.parametrize("n,tokens,heads", list(LAUNCH_CASES))
 def test_encoder_attention_persistent_kernel_matches_per_item_kernel(capi, n, tokens, heads):
     """>= 512 (frame, head) items of 193..208 tokens take the persistent kernel (loader wave + LDS-DMA, two barriers
-    per item); the same frames in chunks below that threshold — and every other token count — take the
-    one-workgroup-per-item kernel: same arithmetic, same bits, whatever the launch geometry."""
+    per item) and of 257 tokens the persistent 257-token kernel; the same frames in chunks of 16 (at most 256 items, below
+    that threshold) take the one-workgroup-per-item kernel: same arithmetic, same bits.  The edges of the plan are in:
+    193 and 208 tokens at 516 items, 257 tokens at exactly 512.  288 and 226 tokens run ONE kernel both ways (ITEM9,
+    STREAM): for them this is that kernel's independence of the launch geometry.  Every call's kernel is asserted."""
     D = heads * 64
+    whole_path, chunk_path = (getattr(capi, "ATTN_" + name) for name in LAUNCH_CASES[n, tokens, heads])
     qkv = rnd(n * tokens, 3 * D, seed=23).to(torch.bfloat16).cuda()
     qkv[:, :D] *= 2.0
     whole = torch.empty(n * tokens, D, device="cuda", dtype=torch.bfloat16)
     capi.attention_fwd(qkv, whole, n, tokens, heads)
+    assert capi.attention_last_path() == whole_path
     parts = torch.empty_like(whole)
     step = 16  # at most 256 items per call
     for f0 in range(0, n, step):
         f1 = min(n, f0 + step)
         capi.attention_fwd(qkv[f0 * tokens:f1 * tokens], parts[f0 * tokens:f1 * tokens], f1 - f0, tokens, heads)
+        assert capi.attention_last_path() == chunk_path
     assert torch.equal(whole, parts)
     again = torch.empty_like(whole)
     capi.attention_fwd(qkv, again, n, tokens, heads)
+    assert capi.attention_last_path() == whole_path
     assert torch.equal(whole, again)
 
 
@@ -612,10 +631,12 @@ def test_encoder_attention_257_tokens_stress(capi):
         qkv = rnd(n * tokens, 3 * D, seed=seed).to(torch.bfloat16).cuda()
         whole = torch.empty(n * tokens, D, device="cuda", dtype=torch.bfloat16)
         capi.attention_fwd(qkv, whole, n, tokens, heads)
+        assert capi.attention_last_path() == capi.ATTN_XROW
         parts = torch.empty_like(whole)
         step = 16  # 256 items per call: below the persistent kernel's threshold
         for f0 in range(0, n, step):
             capi.attention_fwd(qkv[f0 * tokens:(f0 + step) * tokens], parts[f0 * tokens:(f0 + step) * tokens], step, tokens, heads)
+            assert capi.attention_last_path() == capi.ATTN_ITEM9
         bad = (whole != parts)
         assert not bad.any(), f"seed {seed}: {int(bad.sum())} elements differ, first at {bad.nonzero()[0].tolist()}"
 
