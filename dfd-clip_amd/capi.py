@@ -20,7 +20,7 @@ ABI_VERSION = 17
 _DTYPE = {torch.float32: F32, torch.bfloat16: BF16}
 FP8 = 2           # ABI code of OCP e4m3; stored in uint8 / torch.float8_e4m3fn tensors
 FP8_MAX = 448.0   # largest finite e4m3 value
-FP8_MIN_ROWS = 1024  # dfd_gemm_fp8 serves M >= 1024 (include/dfdclip.h)
+FP8_MIN_ROWS = 1024  # dfd_gemm_fp8 serves M >= 1024 (gemm_plan's rule; tests/test_abi_cpu.py holds this constant to it)
 
 
 class DfdError(RuntimeError):
@@ -201,7 +201,17 @@ class AttentionPlan(Structure):
     _fields_ = [("path", c_int32), ("grid", c_uint32), ("block", c_uint32), ("chunk", c_int32), ("lds", c_uint64)]
 
 
+class GemmPlan(Structure):
+    """dfd_gemm_plan_t (include/dfdclip_hooks.h)."""
+    _fields_ = [("kernel", c_int32), ("epilogue", c_int32), ("tile_rows", c_int32), ("tiles_m", c_int32), ("ntiles", c_int64),
+                ("grid", c_uint32), ("grid_y", c_uint32), ("block", c_uint32), ("c_blocked", c_int32), ("a_blocked", c_int32),
+                ("dynamic", c_int32)]
+
+
 HOOK_SIGNATURES = {
+    "dfd_gemm_last_kernel": (c_int, []),
+    "dfd_gemm_plan": (c_int, [c_int, c_int, c_int, c_int64, c_int, c_int, c_int64, c_int64, c_int64, c_uint32, c_int, c_int, c_int, c_uint,
+                              c_uint, c_int, POINTER(GemmPlan)]),
     "dfd_attention_set_variant": (c_int, [c_int]),
     "dfd_attention_last_path": (c_int, []),
     "dfd_attention_plan": (c_int, [c_int, c_int, c_int, c_int, c_int64, c_int64, c_int, POINTER(AttentionPlan)]),
@@ -216,6 +226,12 @@ HOOK_SIGNATURES = {
 # kernels behind dfd_attention_fwd (DFD_ATTN_* of include/dfdclip_hooks.h, which holds the selection table)
 (ATTN_ROWS, ATTN_ROWS_CHUNKED, ATTN_ITEM7, ATTN_ITEM9, ATTN_PERSIST7_SHORT, ATTN_PERSIST7, ATTN_XROW,
  ATTN_STREAM) = range(1, 9)
+
+# kernels behind dfd_gemm / dfd_gemm_fp8 (DFD_GEMM_* of include/dfdclip_hooks.h, which holds the selection table), and the
+# pointer bits of dfd_gemm_plan
+GEMM_GENERAL, GEMM_TILE, GEMM_PERSISTENT, GEMM_PINGPONG = range(1, 5)
+(GEMM_PTR_A, GEMM_PTR_W, GEMM_PTR_C, GEMM_PTR_BIAS, GEMM_PTR_POS, GEMM_PTR_CLS, GEMM_PTR_RESIDUAL, GEMM_PTR_COL_SCALE,
+ GEMM_PTR_EXPORT) = (1 << i for i in range(9))
 
 # families of dfd_stream_policy_set (include/dfdclip_hooks.h)
 STREAM_DECODER_KV, STREAM_DECODER_WEIGHTS, STREAM_OPTIMIZER, STREAM_ENCODER_ROWS, STREAM_ALL = 1, 2, 4, 8, 15
@@ -567,8 +583,27 @@ def stream_policy_get():
 
 
 def gemm_last_path():
-    """256 when this thread's last gemm ran on the tuned 256x256 bf16 kernel, 128 for the general kernel."""
+    """257 / 256 when this thread's last gemm ran on the ping-pong / another tuned 256x256 bf16 kernel, 128 for the general kernel."""
     return load_library().dfd_gemm_last_path()
+
+
+def gemm_last_kernel():
+    """GEMM_* of this thread's last `gemm` or `gemm_fp8` that launched a kernel; 0 = none yet."""
+    return load_library().dfd_gemm_last_kernel()
+
+
+def gemm_plan(ab_dtype, c_dtype, epilogue, M, N, K, lda=None, ldw=None, ldc=None, flags=0, tokens=0, frames_per_clip=0, qkv_first=0,
+              has=0, misaligned=0, n_cu=256):
+    """What `gemm` (ab_dtype F32 / BF16) or `gemm_fp8` (FP8) would do with this call under the thread's variants: a GemmPlan,
+    or DfdError for what the entry point refuses.  Dtypes are ABI codes; dense rows unless a leading dimension is given;
+    `flags` as GemmExtra.flags; `has` / `misaligned`: GEMM_PTR_* bits.  No pointer and, with `n_cu` > 0, no device."""
+    out = GemmPlan()
+    rc = load_library().dfd_gemm_plan(ab_dtype, c_dtype, epilogue, M, N, K, K if lda is None else lda, K if ldw is None else ldw,
+                                      N if ldc is None else ldc, flags, tokens, frames_per_clip, qkv_first, has, misaligned, n_cu,
+                                      ctypes.byref(out))
+    if rc < 0:
+        raise DfdError(f"dfd_gemm_plan failed ({rc}): {load_library().dfd_last_error().decode()}")
+    return out
 
 
 def gemm_at_b_workspace_bytes(R, Ma, Nb, dtype):

@@ -11,9 +11,8 @@
 //
 // Both A and W are K-contiguous, so both MFMA operands are plain 16-byte row reads: lane
 // (r = lane&31, h = lane>>5) holds A[row r][k-slice h] and W[row r][k-slice h].
-#include "gemm_args.hpp"
+#include "gemm_plan.hpp"
 #include "gelu.hpp"
-#include "../../include/dfdclip_hooks.h"
 
 namespace {
 
@@ -190,14 +189,13 @@ __global__ __launch_bounds__(256) void gemm128_kernel(const GemmArgs a) {
       }
 }
 
+// (epilogue) -> instantiation; BIAS_RESIDUAL and PATCH_EMBED exist for an f32 C only (gemm_general_refuses, gemm_plan.hpp)
 template <typename T, typename CT>
-int launch_gemm128(const GemmArgs& a, int epi, hipStream_t st) {
-  const dim3 grid((a.N + BN - 1) / BN, (unsigned)((a.M + BM - 1) / BM)), block(256);
-#define EPI_CASE(E)                                                                    \
-  case E:                                                                              \
-    hipLaunchKernelGGL((gemm128_kernel<T, CT, E>), grid, block, 0, st, a);             \
-    break;
-  switch (epi) {
+int launch_gemm128(const GemmPlan& p, const GemmArgs& a, hipStream_t st) {
+#define EPI_CASE(E) \
+  case E:           \
+    return gemm_launch<&gemm128_kernel<T, CT, E>>("general", p, st, a);
+  switch (p.epilogue) {
     EPI_CASE(DFD_EPI_BIAS)
     EPI_CASE(DFD_EPI_BIAS_QUICKGELU)
     EPI_CASE(DFD_EPI_BIAS_GELU)
@@ -205,21 +203,14 @@ int launch_gemm128(const GemmArgs& a, int epi, hipStream_t st) {
     EPI_CASE(DFD_EPI_RESIDUAL_POS)
     default:
       if constexpr (sizeof(CT) == 4) {
-        switch (epi) {
+        switch (p.epilogue) {
           EPI_CASE(DFD_EPI_BIAS_RESIDUAL)
           EPI_CASE(DFD_EPI_PATCH_EMBED)
-          default:
-            dfd_set_error("dfd_gemm: unknown epilogue %d", epi);
-            return DFD_ERR_INVALID_ARG;
         }
-      } else {
-        dfd_set_error("dfd_gemm: epilogue %d needs an f32 C", epi);
-        return DFD_ERR_INVALID_ARG;
       }
+      return DFD_ERR_INVALID_ARG;  // not reached: the plan names no other epilogue
   }
 #undef EPI_CASE
-  DFD_CHECK_LAUNCH("dfd_gemm");
-  return DFD_OK;
 }
 
 // ---- C = Aᵀ·B for tall operands (weight gradients): transposes + split-K on the kernel above ----------
@@ -280,50 +271,97 @@ int launch_at_b(const void* A, int64_t lda, const void* B, int64_t ldb, float* C
 
 }  // namespace
 
-// epilogue-specific argument checks + copy of dfd_gemm_extra into the kernels' argument block
-static int fill_extra(GemmArgs& a, int epilogue, const dfd_gemm_extra* extra, int c_dtype, int64_t ldc, int64_t M, int N) {
-  if (epilogue == DFD_EPI_PATCH_EMBED) {
-    DFD_REQUIRE(extra && extra->pos && extra->cls && extra->tokens > 1, "dfd_gemm: PATCH_EMBED needs extra.pos, extra.cls, extra.tokens");
-    DFD_REQUIRE(M % (extra->tokens - 1) == 0, "dfd_gemm: PATCH_EMBED M=%lld is not a whole number of frames", (long long)M);
-    DFD_REQUIRE(c_dtype == DFD_F32 && ldc >= N, "dfd_gemm: PATCH_EMBED writes an f32 token matrix");
-  } else {
-    DFD_REQUIRE(ldc >= N, "dfd_gemm: ldc=%lld < N", (long long)ldc);
-  }
-  if (epilogue == DFD_EPI_QKV_EXPORT) {
-    DFD_REQUIRE(extra && extra->tokens > 1 && (extra->qkv_first == 0 || extra->qkv_first == 1) && N % (3 - extra->qkv_first) == 0,
-                "dfd_gemm: QKV_EXPORT needs extra.tokens, qkv_first in {0, 1} and N a multiple of the column blocks present");
-    DFD_REQUIRE(M % extra->tokens == 0, "dfd_gemm: QKV_EXPORT M=%lld is not a whole number of frames", (long long)M);
-    DFD_REQUIRE(!extra->k_export == !extra->v_export, "dfd_gemm: QKV_EXPORT needs both k_export and v_export or neither");
-    DFD_REQUIRE(!extra->pos || extra->frames_per_clip > 0, "dfd_gemm: QKV_EXPORT with pos needs frames_per_clip");
-  }
-  if (epilogue == DFD_EPI_RESIDUAL_POS) {
-    DFD_REQUIRE(extra && extra->tokens > 1, "dfd_gemm: RESIDUAL_POS needs extra.tokens (patches per frame + 1)");
-    DFD_REQUIRE(!extra->pos || extra->frames_per_clip > 0, "dfd_gemm: RESIDUAL_POS with pos needs frames_per_clip");
-  }
-  if (extra) {
-    a.pos = extra->pos; a.cls = extra->cls; a.k_export = extra->k_export; a.v_export = extra->v_export;
-    a.residual = epilogue == DFD_EPI_RESIDUAL_POS ? extra->residual : nullptr;
-    a.tokens = extra->tokens; a.frames_per_clip = extra->frames_per_clip > 0 ? extra->frames_per_clip : 1;
-    a.qkv_first = epilogue == DFD_EPI_QKV_EXPORT ? extra->qkv_first : 0;
-    a.stream_out = (extra->flags & DFD_GEMM_STREAM_OUT) ? 1 : 0;
-    a.spare_cus = (int)((extra->flags >> DFD_GEMM_SPARE_CUS_SHIFT) & 0xff);
-    a.spare_if_free = (extra->flags & DFD_GEMM_SPARE_IF_FREE) ? 1 : 0;
-    a.tile_rows = 32 * (int)((extra->flags >> DFD_GEMM_TILE_BLOCKS_SHIFT) & 0xf);
-    a.c_blocked = (extra->flags & DFD_GEMM_C_BLOCKED) ? 1 : 0;
-    a.a_blocked = (extra->flags & DFD_GEMM_A_BLOCKED) ? 1 : 0;
-    a.pair = a.c_blocked | a.a_blocked;
-    DFD_REQUIRE(a.tile_rows == 0 || a.tile_rows == 224 || a.tile_rows == 256, "dfd_gemm: tile blocks must be 0, 7 or 8");
-    if (epilogue == DFD_EPI_RESIDUAL_POS && extra->drop_rng && extra->drop_p > 0.f) {
-      DFD_REQUIRE(extra->drop_p < 1.f, "dfd_gemm: drop_p=%f", (double)extra->drop_p);
-      const dfd_dropout_t dd{extra->drop_rng, extra->drop_site, extra->drop_p};
-      a.drop = dfd_make_drop(&dd);
-    }
+// copy of dfd_gemm_extra into the kernels' argument block, and the two checks that need its pointers or its dropout
+static int fill_extra(GemmArgs& a, int epilogue, const dfd_gemm_extra* extra) {
+  if (!extra) return DFD_OK;
+  a.pos = extra->pos; a.cls = extra->cls; a.k_export = extra->k_export; a.v_export = extra->v_export;
+  a.residual = epilogue == DFD_EPI_RESIDUAL_POS ? extra->residual : nullptr;
+  a.tokens = extra->tokens; a.frames_per_clip = extra->frames_per_clip;
+  a.qkv_first = epilogue == DFD_EPI_QKV_EXPORT ? extra->qkv_first : 0;
+  a.stream_out = (extra->flags & DFD_GEMM_STREAM_OUT) ? 1 : 0;
+  a.spare_cus = (int)((extra->flags >> DFD_GEMM_SPARE_CUS_SHIFT) & 0xff);
+  a.spare_if_free = (extra->flags & DFD_GEMM_SPARE_IF_FREE) ? 1 : 0;
+  a.tile_rows = 32 * (int)((extra->flags >> DFD_GEMM_TILE_BLOCKS_SHIFT) & 0xf);
+  a.c_blocked = (extra->flags & DFD_GEMM_C_BLOCKED) ? 1 : 0;
+  a.a_blocked = (extra->flags & DFD_GEMM_A_BLOCKED) ? 1 : 0;
+  a.pair = a.c_blocked | a.a_blocked;
+  DFD_REQUIRE(epilogue != DFD_EPI_QKV_EXPORT || !extra->k_export == !extra->v_export, "dfd_gemm: QKV_EXPORT needs both k_export and v_export or neither");
+  if (epilogue == DFD_EPI_RESIDUAL_POS && extra->drop_rng && extra->drop_p > 0.f) {
+    DFD_REQUIRE(extra->drop_p < 1.f, "dfd_gemm: drop_p=%f", (double)extra->drop_p);
+    const dfd_dropout_t dd{extra->drop_rng, extra->drop_site, extra->drop_p};
+    a.drop = dfd_make_drop(&dd);
   }
   return DFD_OK;
 }
 
-static thread_local int g_last_path = 0;
 static thread_local int g_gemm_variant = 0;
+static thread_local int g_pair_variant = 0;
+
+// What dfd_gemm (`who`; ab_dtype F32 / BF16) and dfd_gemm_fp8 (FP8) refuse about the numbers of a call, then the plan for
+// what they accept (kernel 0 for M == 0: nothing to launch), or the refusal in the entry point's words.  Shared with the
+// dfd_gemm_plan hook, so it reads `ptrs` and never a pointer.  n_cu <= 0: the current device's.
+static int checked_plan(GemmPlan* p, const char* who, GemmArgs& a, GemmPtrs ptrs, int ab_dtype, int c_dtype, int epilogue, int n_cu) {
+  const bool f8 = ab_dtype == DFD_FP8;
+  DFD_REQUIRE(a.M >= 0 && a.N > 0 && a.K > 0, "%s: bad shape M=%lld N=%d K=%d", who, (long long)a.M, a.N, a.K);
+  if (f8) {
+    DFD_REQUIRE(c_dtype == DFD_BF16 || c_dtype == DFD_FP8, "%s: c_dtype=%d", who, c_dtype);
+    DFD_REQUIRE(epilogue == DFD_EPI_BIAS || epilogue == DFD_EPI_BIAS_QUICKGELU || epilogue == DFD_EPI_BIAS_GELU || epilogue == DFD_EPI_QKV_EXPORT,
+                "%s: epilogue %d not served (BIAS, BIAS_QUICKGELU, BIAS_GELU, QKV_EXPORT)", who, epilogue);
+    DFD_REQUIRE(c_dtype == DFD_BF16 || (epilogue != DFD_EPI_QKV_EXPORT && a.out_inv_scale > 0.f), "%s: fp8 output needs out_inv_scale > 0 and a plain / QuickGELU / GELU epilogue", who);
+    DFD_REQUIRE(a.lda >= a.K && a.ldw >= a.K && a.ldc >= a.N, "%s: leading dimensions", who);
+  } else {
+    DFD_REQUIRE(ab_dtype == DFD_F32 || ab_dtype == DFD_BF16, "%s: ab_dtype=%d", who, ab_dtype);
+    DFD_REQUIRE(c_dtype == DFD_F32 || c_dtype == DFD_BF16, "%s: c_dtype=%d", who, c_dtype);
+    DFD_REQUIRE(!(ab_dtype == DFD_F32 && c_dtype == DFD_BF16), "%s: f32 operands with bf16 output unsupported", who);
+    DFD_REQUIRE(a.K % 32 == 0, "%s: K=%d must be a multiple of 32", who, a.K);
+    const int esz = ab_dtype == DFD_F32 ? 4 : 2;
+    DFD_REQUIRE(a.lda >= a.K && a.ldw >= a.K && (a.lda * esz) % 16 == 0 && (a.ldw * esz) % 16 == 0, "%s: lda=%lld ldw=%lld must be >= K and 16-byte multiples", who,
+                (long long)a.lda, (long long)a.ldw);
+    DFD_REQUIRE(!(ptrs.misaligned & (DFD_GEMM_PTR_A | DFD_GEMM_PTR_W)), "%s: A and W must be 16-byte aligned", who);
+  }
+  // epilogue-specific arguments
+  const bool has_pos = ptrs.present & DFD_GEMM_PTR_POS;
+  if (epilogue == DFD_EPI_PATCH_EMBED) {
+    DFD_REQUIRE(has_pos && (ptrs.present & DFD_GEMM_PTR_CLS) && a.tokens > 1, "%s: PATCH_EMBED needs extra.pos, extra.cls, extra.tokens", who);
+    DFD_REQUIRE(a.M % (a.tokens - 1) == 0, "%s: PATCH_EMBED M=%lld is not a whole number of frames", who, (long long)a.M);
+    DFD_REQUIRE(c_dtype == DFD_F32 && a.ldc >= a.N, "%s: PATCH_EMBED writes an f32 token matrix", who);
+  } else {
+    DFD_REQUIRE(a.ldc >= a.N, "%s: ldc=%lld < N", who, (long long)a.ldc);
+  }
+  if (epilogue == DFD_EPI_QKV_EXPORT) {
+    DFD_REQUIRE(a.tokens > 1 && (a.qkv_first == 0 || a.qkv_first == 1) && a.N % (3 - a.qkv_first) == 0,
+                "%s: QKV_EXPORT needs extra.tokens, qkv_first in {0, 1} and N a multiple of the column blocks present", who);
+    DFD_REQUIRE(a.M % a.tokens == 0, "%s: QKV_EXPORT M=%lld is not a whole number of frames", who, (long long)a.M);
+    DFD_REQUIRE(!has_pos || a.frames_per_clip > 0, "%s: QKV_EXPORT with pos needs frames_per_clip", who);
+  }
+  if (epilogue == DFD_EPI_RESIDUAL_POS) {
+    DFD_REQUIRE(a.tokens > 1, "%s: RESIDUAL_POS needs extra.tokens (patches per frame + 1)", who);
+    DFD_REQUIRE(!has_pos || a.frames_per_clip > 0, "%s: RESIDUAL_POS with pos needs frames_per_clip", who);
+  }
+  DFD_REQUIRE(a.tile_rows == 0 || a.tile_rows == 224 || a.tile_rows == 256, "%s: tile blocks must be 0, 7 or 8", who);
+  if (a.frames_per_clip < 1) a.frames_per_clip = 1;
+  if (a.M == 0) {
+    *p = GemmPlan{};
+    return DFD_OK;
+  }
+  *p = gemm_plan(a, ptrs, ab_dtype, c_dtype, epilogue, g_gemm_variant, g_pair_variant, n_cu > 0 ? n_cu : dfd_cu_count());
+  if (p->refused) {
+    dfd_set_error("%s: %s%s (epilogue %d, M=%lld N=%d K=%d)", who,
+                  a.pair ? "DFD_GEMM_C_BLOCKED / DFD_GEMM_A_BLOCKED: the ping-pong kernel does not serve this call: " : "call not served: ", p->refused,
+                  epilogue, (long long)a.M, a.N, a.K);
+    return DFD_ERR_INVALID_ARG;
+  }
+  if (p->tiles.grid == 0) {
+    dfd_set_error("%s: cannot query the device", who);
+    return DFD_ERR_LAUNCH;
+  }
+  return DFD_OK;
+}
+
+// Which kernel served this thread's last successful call; dfd_gemm_last_path is dfd_gemm's share of it, in its own numbers
+static thread_local int g_last_kernel = 0;
+static thread_local int g_last_path = 0;
+extern "C" int dfd_gemm_last_kernel(void) { return g_last_kernel; }
 extern "C" int dfd_gemm_last_path(void) { return g_last_path; }
 extern "C" int dfd_gemm_set_variant(int variant) {
   const int old = g_gemm_variant;
@@ -332,7 +370,6 @@ extern "C" int dfd_gemm_set_variant(int variant) {
 }
 
 // ---- the c_fc -> c_proj pair with a fragment-blocked intermediate (gemm_blocked.hpp; hooks: include/dfdclip_hooks.h) ----
-static thread_local int g_pair_variant = 0;
 static thread_local int64_t g_pair_launches = 0;
 extern "C" int dfd_gemm_pair_set_variant(int variant) {
   const int old = g_pair_variant;
@@ -340,108 +377,91 @@ extern "C" int dfd_gemm_pair_set_variant(int variant) {
   return old;
 }
 extern "C" int64_t dfd_gemm_pair_launches(void) { return g_pair_launches; }
-// Both halves are put to the ping-pong kernel's own eligibility check (dfd_gemm256e_serves: the rules the launcher
-// applies to the flagged calls) as dense bf16 matrices at 16-byte aligned addresses, so the plan cannot promise what the
-// launcher refuses.  What the plan adds is policy: below 1,024 rows the pair stays with the kernels that serve small M
-// (variant 2 waives that, for tests), and the skip-the-ping-pong variant of dfd_gemm_set_variant leaves no kernel that
-// knows the layout.
+// Both halves are put to gemm_plan as the flagged calls of dense bf16 matrices with every pointer aligned, so the pair's
+// plan cannot promise what dfd_gemm refuses (under the skip-the-ping-pong variant of dfd_gemm_set_variant, say, which leaves
+// no kernel that knows the layout).  What it adds is policy: below 1,024 rows the pair stays with the kernels that serve
+// small M (variant 2 waives that, for tests).
 extern "C" int dfd_gemm_pair_plan(int64_t M, int D, int H) {
-  if (g_pair_variant == 1 || g_gemm_variant == 1 || M < 1 || D < 1 || H < 1) return 0;
+  if (g_pair_variant == 1 || M < 1 || D < 1 || H < 1) return 0;
   if (M < 1024 && g_pair_variant != 2) return 0;
-  void* const any = reinterpret_cast<void*>(uintptr_t{256});  // an aligned address: nothing is dereferenced
   GemmArgs fc{}, pr{};
-  fc.A = pr.A = any; fc.W = pr.W = any; fc.C = pr.C = any;
   fc.M = pr.M = M; fc.pair = pr.pair = 1;
   fc.N = H; fc.K = D; fc.lda = D; fc.ldw = D; fc.ldc = H; fc.c_blocked = 1;
   pr.N = D; pr.K = H; pr.lda = H; pr.ldw = H; pr.ldc = D; pr.a_blocked = 1;
-  // (QuickGELU and the erf GELU share every rule that depends on the epilogue)
-  return dfd_gemm256e_serves(fc, DFD_BF16, DFD_EPI_BIAS_QUICKGELU) && dfd_gemm256e_serves(pr, DFD_BF16, DFD_EPI_BIAS) ? 1 : 0;
+  const GemmPtrs dense{DFD_GEMM_PTR_A | DFD_GEMM_PTR_W | DFD_GEMM_PTR_C | DFD_GEMM_PTR_BIAS, 0u};
+  // (QuickGELU and the erf GELU share every rule that depends on the epilogue; the kernel does not depend on the CU count)
+  auto blocked = [&](const GemmArgs& a, int epi) {
+    return gemm_plan(a, dense, DFD_BF16, DFD_BF16, epi, g_gemm_variant, g_pair_variant, 256).kernel == DFD_GEMM_PINGPONG;
+  };
+  return blocked(fc, DFD_EPI_BIAS_QUICKGELU) && blocked(pr, DFD_EPI_BIAS) ? 1 : 0;
 }
 
-// The two persistent kernels in their order: gemm256e.hip (ping-pong K loop: K / step even and >= 6), then gemm256p.hip
-// (the other depths; variant 1 goes there at once).  0 = launched (*path = 257 / 256), <0 = error, 1 = neither serves it.
-static int try_persistent_kernels(GemmArgs& a, int c_dtype, int epilogue, bool f8, hipStream_t st, int* path) {
-  // a q|k|v projection without an export is a plain biased store
-  const int epi_p = epilogue == DFD_EPI_QKV_EXPORT && a.k_export == nullptr ? DFD_EPI_BIAS : epilogue;
-  a.no_dynamic = g_gemm_variant != 3;
-  if (a.pair) {
-    // one half of a c_fc -> c_proj pair: this kernel or none (pair variant 1: the same kernel, row-major)
-    if (g_pair_variant == 1) a.c_blocked = a.a_blocked = 0;
-    *path = 257;
-    const int rc = f8 || g_gemm_variant == 1 ? 1 : dfd_gemm256e_try(a, c_dtype, epi_p, st);
-    if (rc == 1) {
-      dfd_set_error("dfd_gemm: DFD_GEMM_C_BLOCKED / DFD_GEMM_A_BLOCKED: the ping-pong kernel does not serve this call (bf16, N %% 256 == 0, "
-                    "K %% 128 == 0, K >= 384, ld %% 64 == 0, BIAS_QUICKGELU / BIAS_GELU for C, BIAS for A; got M=%lld N=%d K=%d)",
-                    (long long)a.M, a.N, a.K);
-      return DFD_ERR_INVALID_ARG;
-    }
-    if (rc == 0 && (a.c_blocked || a.a_blocked)) ++g_pair_launches;
-    return rc;
+// validate -> plan -> the planned kernel's launcher -> record
+static int plan_and_launch(const char* who, GemmArgs& a, int ab_dtype, int c_dtype, int epilogue, void* stream) {
+  GemmPlan p;
+  if (const int rc = checked_plan(&p, who, a, gemm_ptrs(a), ab_dtype, c_dtype, epilogue, 0)) return rc;
+  if (p.kernel == 0) return DFD_OK;  // M == 0
+  a.c_blocked = p.c_blocked;
+  a.a_blocked = p.a_blocked;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const bool f8 = ab_dtype == DFD_FP8, cf8 = c_dtype == DFD_FP8;
+  int rc, path;
+  switch (p.kernel) {
+    case DFD_GEMM_PINGPONG: rc = dfd_gemm256e_launch(p, a, f8, cf8, st); path = 257; break;
+    case DFD_GEMM_PERSISTENT: rc = dfd_gemm256p_launch(p, a, f8, cf8, st); path = 256; break;
+    case DFD_GEMM_TILE: rc = dfd_gemm256_launch(p, a, c_dtype, st); path = 256; break;
+    default:  // DFD_GEMM_GENERAL
+      rc = ab_dtype == DFD_F32 ? launch_gemm128<float, float>(p, a, st)
+           : c_dtype == DFD_BF16 ? launch_gemm128<bf16_t, bf16_t>(p, a, st) : launch_gemm128<bf16_t, float>(p, a, st);
+      path = 128;
   }
-  int rc = g_gemm_variant == 1 ? 1 : (f8 ? dfd_gemm256e_f8_try : dfd_gemm256e_try)(a, c_dtype, epi_p, st);
-  *path = 257;
-  if (rc != 1) return rc;
-  rc = (f8 ? dfd_gemm256p_f8_try : dfd_gemm256p_try)(a, c_dtype, epi_p, st);
-  *path = 256;
-  return rc;
+  if (rc != DFD_OK) return rc;
+  g_last_kernel = p.kernel;
+  if (!f8) g_last_path = path;  // (dfd_gemm_last_path reports dfd_gemm's launches only)
+  if (p.c_blocked || p.a_blocked) ++g_pair_launches;
+  return DFD_OK;
+}
+
+extern "C" int dfd_gemm_plan(int ab_dtype, int c_dtype, int epilogue, int64_t M, int N, int K, int64_t lda, int64_t ldw, int64_t ldc,
+                             uint32_t flags, int tokens, int frames_per_clip, int qkv_first, unsigned has, unsigned misaligned, int n_cu,
+                             dfd_gemm_plan_t* out) {
+  dfd_gemm_extra extra{};
+  extra.tokens = tokens; extra.frames_per_clip = frames_per_clip; extra.qkv_first = qkv_first; extra.flags = flags;
+  GemmArgs a{};
+  a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.M = M; a.N = N; a.K = K; a.out_inv_scale = 1.f;
+  (void)fill_extra(a, epilogue, &extra);
+  const unsigned optional = DFD_GEMM_PTR_EXPORT | DFD_GEMM_PTR_POS | DFD_GEMM_PTR_RESIDUAL;
+  GemmPtrs ptrs{((2u * DFD_GEMM_PTR_EXPORT - 1u) & ~optional) | (has & optional), 0u};
+  ptrs.misaligned = misaligned & ptrs.present;
+  GemmPlan p;
+  if (checked_plan(&p, ab_dtype == DFD_FP8 ? "dfd_gemm_fp8" : "dfd_gemm", a, ptrs, ab_dtype, c_dtype, epilogue, n_cu) != DFD_OK) return -1;
+  if (out)
+    *out = dfd_gemm_plan_t{p.kernel, p.epilogue, p.tiles.rows, p.tiles.tiles_m, p.tiles.ntiles, (uint32_t)p.tiles.grid, p.grid_y, p.block,
+                           p.c_blocked, p.a_blocked, p.dynamic};
+  return p.kernel;
 }
 
 extern "C" int dfd_gemm(const void* A, int64_t lda, const void* W, int64_t ldw, int ab_dtype, void* C, int64_t ldc,
                         int c_dtype, const float* bias, int epilogue, const dfd_gemm_extra* extra, int64_t M, int N,
                         int K, void* stream) {
   DFD_REQUIRE(A && W && C, "dfd_gemm: null pointer");
-  DFD_REQUIRE(M >= 0 && N > 0 && K > 0, "dfd_gemm: bad shape M=%lld N=%d K=%d", (long long)M, N, K);
-  DFD_REQUIRE(ab_dtype == DFD_F32 || ab_dtype == DFD_BF16, "dfd_gemm: ab_dtype=%d", ab_dtype);
-  DFD_REQUIRE(c_dtype == DFD_F32 || c_dtype == DFD_BF16, "dfd_gemm: c_dtype=%d", c_dtype);
-  DFD_REQUIRE(!(ab_dtype == DFD_F32 && c_dtype == DFD_BF16), "dfd_gemm: f32 operands with bf16 output unsupported");
-  DFD_REQUIRE(K % 32 == 0, "dfd_gemm: K=%d must be a multiple of 32", K);
-  const int esz = ab_dtype == DFD_F32 ? 4 : 2;
-  DFD_REQUIRE(lda >= K && ldw >= K && (lda * esz) % 16 == 0 && (ldw * esz) % 16 == 0, "dfd_gemm: lda=%lld ldw=%lld must be >= K and 16-byte multiples", (long long)lda, (long long)ldw);
-  DFD_REQUIRE(dfd_aligned16(A) && dfd_aligned16(W), "dfd_gemm: A and W must be 16-byte aligned");
+  DFD_REQUIRE(ab_dtype != DFD_FP8, "dfd_gemm: ab_dtype=%d", ab_dtype);  // (dfd_gemm_fp8's operands)
   GemmArgs a{};
   a.A = A; a.W = W; a.C = C; a.bias = bias;
   a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.M = M; a.N = N; a.K = K;
-  { const int rc = fill_extra(a, epilogue, extra, c_dtype, ldc, M, N); if (rc != DFD_OK) return rc; }
-  if (M == 0) return DFD_OK;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (ab_dtype == DFD_BF16) {
-    int path = 0;
-    int rc = try_persistent_kernels(a, c_dtype, epilogue, false, st, &path);
-    if (rc == 0) g_last_path = path;
-    if (rc <= 0) return rc;
-    rc = dfd_gemm256_try(a, c_dtype, epilogue, st);
-    if (rc == 0) g_last_path = 256;
-    if (rc <= 0) return rc;
-  }
-  g_last_path = 128;
-  if (ab_dtype == DFD_F32) return launch_gemm128<float, float>(a, epilogue, st);
-  if (c_dtype == DFD_BF16) return launch_gemm128<bf16_t, bf16_t>(a, epilogue, st);
-  return launch_gemm128<bf16_t, float>(a, epilogue, st);
+  if (const int rc = fill_extra(a, epilogue, extra)) return rc;
+  return plan_and_launch("dfd_gemm", a, ab_dtype, c_dtype, epilogue, stream);
 }
 
 extern "C" int dfd_gemm_fp8(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, int c_dtype,
                             const float* col_scale, const float* bias, float out_inv_scale, int epilogue,
                             const dfd_gemm_extra* extra, int64_t M, int N, int K, void* stream) {
   DFD_REQUIRE(A && W && C && col_scale, "dfd_gemm_fp8: null pointer");
-  DFD_REQUIRE(M >= 0 && N > 0 && K > 0, "dfd_gemm_fp8: bad shape M=%lld N=%d K=%d", (long long)M, N, K);
-  DFD_REQUIRE(c_dtype == DFD_BF16 || c_dtype == DFD_FP8, "dfd_gemm_fp8: c_dtype=%d", c_dtype);
-  DFD_REQUIRE(epilogue == DFD_EPI_BIAS || epilogue == DFD_EPI_BIAS_QUICKGELU || epilogue == DFD_EPI_BIAS_GELU || epilogue == DFD_EPI_QKV_EXPORT,
-              "dfd_gemm_fp8: epilogue %d not served (BIAS, BIAS_QUICKGELU, BIAS_GELU, QKV_EXPORT)", epilogue);
-  DFD_REQUIRE(c_dtype == DFD_BF16 || (epilogue != DFD_EPI_QKV_EXPORT && out_inv_scale > 0.f), "dfd_gemm_fp8: fp8 output needs out_inv_scale > 0 and a plain / QuickGELU / GELU epilogue");
-  DFD_REQUIRE(lda >= K && ldw >= K && ldc >= N, "dfd_gemm_fp8: leading dimensions");
   GemmArgs a{};
   a.A = A; a.W = W; a.C = C; a.bias = bias; a.col_scale = col_scale; a.out_inv_scale = out_inv_scale;
   a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.M = M; a.N = N; a.K = K;
-  { const int rc = fill_extra(a, epilogue, extra, c_dtype, ldc, M, N); if (rc != DFD_OK) return rc; }
-  if (M == 0) return DFD_OK;
-  int path = 0;  // (dfd_gemm_last_path reports dfd_gemm's launches only)
-  const int rc = try_persistent_kernels(a, c_dtype, epilogue, true, static_cast<hipStream_t>(stream), &path);
-  if (rc == 1) {
-    dfd_set_error("dfd_gemm_fp8: shape not served (needs M >= 1024, N %% 256 == 0, K %% 128 == 0, K >= 256, 16-byte aligned rows; got M=%lld N=%d K=%d)",
-                  (long long)M, N, K);
-    return DFD_ERR_INVALID_ARG;
-  }
-  return rc;
+  if (const int rc = fill_extra(a, epilogue, extra)) return rc;
+  return plan_and_launch("dfd_gemm_fp8", a, DFD_FP8, c_dtype, epilogue, stream);
 }
 
 // gemm_tn.hip: bf16 operands read through the transposing LDS load, no HBM transposes

@@ -27,7 +27,7 @@
 // Rows beyond M are clamped on load and masked on store; N % 256 == 0, K % 64 == 0, K >= 128.
 #include <type_traits>
 
-#include "gemm_args.hpp"
+#include "gemm_plan.hpp"
 
 namespace {
 
@@ -427,46 +427,29 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmArgs a, int tile
 }
 
 template <typename CT, int EPI>
-int launch256(const GemmArgs& a, hipStream_t st) {
-  const int tiles_n = a.N / TN;
-  const int tiles_m = (int)((a.M + TM - 1) / TM);
-  hipLaunchKernelGGL((gemm256_kernel<CT, EPI>), dim3(tiles_m * tiles_n), dim3(512), 0, st, a, tiles_n);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    dfd_set_error("dfd_gemm(tuned bf16): launch failed: %s", hipGetErrorString(e));
-    return DFD_ERR_LAUNCH;
-  }
-  return DFD_OK;
+int launch256(const GemmPlan& p, const GemmArgs& a, hipStream_t st) {
+  return gemm_launch<&gemm256_kernel<CT, EPI>>("tuned bf16", p, st, a, a.N / TN);
 }
 
 }  // namespace
 
-int dfd_gemm256_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st) {
-  if (a.N % TN != 0 || a.K % 64 != 0 || a.K < 128 || a.M < 1024) return 1;
-  if ((a.lda % 8) != 0 || (a.ldw % 8) != 0 || (a.ldc % 4) != 0) return 1;
-  if ((reinterpret_cast<uintptr_t>(a.C) & 15) != 0) return 1;
-  if (a.bias && (reinterpret_cast<uintptr_t>(a.bias) & 15) != 0) return 1;
-  if ((int64_t)((a.M + TM - 1) / TM) * (a.N / TN) > 0x7fffffff) return 1;
-  if (a.M >= ((int64_t)1 << 31)) return 1;  // the epilogues index rows with 32-bit arithmetic
-  switch (epi) {
+// (epilogue, C type) -> instantiation; which of them exist for which C type is gemm_tile_refuses' knowledge (gemm_plan.hpp)
+int dfd_gemm256_launch(const GemmPlan& p, const GemmArgs& a, int c_dtype, hipStream_t st) {
+  const bool bf = c_dtype == DFD_BF16;
+  switch (p.epilogue) {
     case DFD_EPI_BIAS:
-      return c_dtype == DFD_BF16 ? launch256<bf16_t, DFD_EPI_BIAS>(a, st) : launch256<float, DFD_EPI_BIAS>(a, st);
+      return bf ? launch256<bf16_t, DFD_EPI_BIAS>(p, a, st) : launch256<float, DFD_EPI_BIAS>(p, a, st);
     case DFD_EPI_BIAS_QUICKGELU:
-      return c_dtype == DFD_BF16 ? launch256<bf16_t, DFD_EPI_BIAS_QUICKGELU>(a, st) : launch256<float, DFD_EPI_BIAS_QUICKGELU>(a, st);
+      return bf ? launch256<bf16_t, DFD_EPI_BIAS_QUICKGELU>(p, a, st) : launch256<float, DFD_EPI_BIAS_QUICKGELU>(p, a, st);
     case DFD_EPI_QKV_EXPORT:
-      if ((a.N / (3 - a.qkv_first)) % TN != 0) return 1;
-      if (a.pos && (reinterpret_cast<uintptr_t>(a.pos) & 15) != 0) return 1;
-      return c_dtype == DFD_BF16 ? launch256<bf16_t, DFD_EPI_QKV_EXPORT>(a, st) : launch256<float, DFD_EPI_QKV_EXPORT>(a, st);
+      return bf ? launch256<bf16_t, DFD_EPI_QKV_EXPORT>(p, a, st) : launch256<float, DFD_EPI_QKV_EXPORT>(p, a, st);
     case DFD_EPI_BIAS_RESIDUAL:
-      return c_dtype == DFD_F32 ? launch256<float, DFD_EPI_BIAS_RESIDUAL>(a, st) : 1;
+      return launch256<float, DFD_EPI_BIAS_RESIDUAL>(p, a, st);
     case DFD_EPI_RESIDUAL_POS:
-      if (a.pos && (reinterpret_cast<uintptr_t>(a.pos) & 15) != 0) return 1;
-      if ((a.ldc % 8) != 0 || (reinterpret_cast<uintptr_t>(a.residual) & 15) != 0) return 1;
-      return c_dtype == DFD_BF16 ? launch256<bf16_t, DFD_EPI_RESIDUAL_POS>(a, st) : 1;
+      return launch256<bf16_t, DFD_EPI_RESIDUAL_POS>(p, a, st);
     case DFD_EPI_PATCH_EMBED:
-      if ((reinterpret_cast<uintptr_t>(a.pos) & 15) != 0 || (reinterpret_cast<uintptr_t>(a.cls) & 15) != 0) return 1;
-      return c_dtype == DFD_F32 ? launch256<float, DFD_EPI_PATCH_EMBED>(a, st) : 1;
+      return launch256<float, DFD_EPI_PATCH_EMBED>(p, a, st);
     default:
-      return 1;
+      return DFD_ERR_INVALID_ARG;  // not reached: the plan names no other epilogue
   }
 }

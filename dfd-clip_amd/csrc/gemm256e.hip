@@ -483,40 +483,22 @@ bool sched_prepare(GemmArgs& a, hipStream_t st, int grid, int64_t ntiles) {
 }
 
 struct Gemm256e {
-  static constexpr const char* name = "ping-pong";
-  static constexpr bool spare_if_free = true;
-  static constexpr bool blocked_layout = true;  // gemm_blocked.hpp
-  static constexpr bool serves(int epi, bool f8) {
-    return epi == DFD_EPI_BIAS || epi == DFD_EPI_BIAS_QUICKGELU || epi == DFD_EPI_BIAS_GELU || epi == DFD_EPI_QKV_EXPORT || (!f8 && epi == DFD_EPI_RESIDUAL_POS);
-  }
-  // the loop is unrolled in pairs of K tiles around a head of two and a tail of four (RESIDUAL_POS: also the short form, 4)
-  static bool depth_ok(const GemmArgs& a, int esz, int nk, int epi) {
-    if ((nk < 6 && !(epi == DFD_EPI_RESIDUAL_POS && nk == 4)) || (nk & 1)) return false;
-    return (a.ldw * esz) % 128 == 0;  // the second piece of a W unit is addressed as (first ^ 64) + 8 rows
-  }
-  static void prepare(GemmArgs& a, hipStream_t st, const TilePlan& p, bool f8) {
-    if (!f8 && a.K / TK >= 6 && a.no_dynamic == 0) sched_prepare(a, st, p.grid, p.ntiles);
-    else a.sched = nullptr;
-  }
+  static constexpr int kernel = DFD_GEMM_PINGPONG;
   template <int EPI, int RB, bool F8, bool CF8>
-  static void run(int grid, hipStream_t st, const GemmArgs& a, int tiles_m, int tiles_n) {
+  static int run(const GemmPlan& p, hipStream_t st, const GemmArgs& a) {
     if constexpr (!F8 && EPI == DFD_EPI_BIAS) {
-      if (a.a_blocked) {  // c_proj reading the fragment-blocked `u`: the instantiation that knows the layout
-        hipLaunchKernelGGL((gemm256e_kernel<EPI, RB, F8, CF8, true>), dim3(grid), dim3(512), 0, st, a, tiles_m, tiles_n);
-        return;
-      }
+      // c_proj reading the fragment-blocked `u`: the instantiation that knows the layout
+      if (a.a_blocked) return gemm_launch<&gemm256e_kernel<EPI, RB, F8, CF8, true>>("ping-pong", p, st, a, p.tiles.tiles_m, a.N / TN);
     }
-    hipLaunchKernelGGL((gemm256e_kernel<EPI, RB, F8, CF8, false>), dim3(grid), dim3(512), 0, st, a, tiles_m, tiles_n);
+    return gemm_launch<&gemm256e_kernel<EPI, RB, F8, CF8, false>>("ping-pong", p, st, a, p.tiles.tiles_m, a.N / TN);
   }
 };
 
 }  // namespace
 
-// 0 = launched, <0 = error, 1 = shape / epilogue not served by this kernel
-int dfd_gemm256e_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st) { return try_persistent<Gemm256e, false>(a, c_dtype, epi, st); }
-
-// 1 = this kernel would serve the bf16 call (shape, leading dimensions, alignment, epilogue, layout flags); nothing is launched
-int dfd_gemm256e_serves(const GemmArgs& a, int c_dtype, int epi) { return persistent_serves<Gemm256e, false>(a, c_dtype, epi) == 0; }
-
-// fp8 (e4m3) operands on the block-scaled matrix cores; C bf16, or e4m3 for the plain / QuickGELU / GELU epilogues
-int dfd_gemm256e_f8_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st) { return try_persistent<Gemm256e, true>(a, c_dtype, epi, st); }
+// f8: e4m3 operands on the block-scaled matrix cores; cf8: C as e4m3 (the plain / QuickGELU / GELU epilogues)
+int dfd_gemm256e_launch(const GemmPlan& p, GemmArgs& a, bool f8, bool cf8, hipStream_t st) {
+  if (p.dynamic) sched_prepare(a, st, p.tiles.grid, p.tiles.ntiles);
+  else a.sched = nullptr;
+  return launch_persistent<Gemm256e>(p, a, f8, cf8, st);
+}

@@ -353,24 +353,14 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(const GemmArgs a, int til
 }
 
 struct Gemm256p {
-  static constexpr const char* name = "persistent";
-  static constexpr bool spare_if_free = false;  // spare_cus is taken as given
-  static constexpr bool blocked_layout = false;  // gemm_blocked.hpp: gemm256e.hip's pair only
-  static constexpr bool serves(int epi, bool f8) {
-    return epi == DFD_EPI_BIAS || epi == DFD_EPI_BIAS_QUICKGELU || epi == DFD_EPI_QKV_EXPORT || (f8 && epi == DFD_EPI_BIAS_GELU);
-  }
-  static bool depth_ok(const GemmArgs&, int, int nk, int) { return nk >= 2; }
-  static void prepare(GemmArgs&, hipStream_t, const TilePlan&, bool) {}
+  static constexpr int kernel = DFD_GEMM_PERSISTENT;
   template <int EPI, int RB, bool F8, bool CF8>
-  static void run(int grid, hipStream_t st, const GemmArgs& a, int tiles_m, int tiles_n) {
-    hipLaunchKernelGGL((gemm256p_kernel<EPI, RB, F8, CF8>), dim3(grid), dim3(512), 0, st, a, tiles_m, tiles_n);
+  static int run(const GemmPlan& p, hipStream_t st, const GemmArgs& a) {
+    return gemm_launch<&gemm256p_kernel<EPI, RB, F8, CF8>>("persistent", p, st, a, p.tiles.tiles_m, a.N / TN);
   }
 };
 
 }  // namespace
 
-// 0 = launched, <0 = error, 1 = shape / epilogue not served by this kernel
-int dfd_gemm256p_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st) { return try_persistent<Gemm256p, false>(a, c_dtype, epi, st); }
-
-// fp8 (e4m3) operands on the block-scaled matrix cores; C bf16, or e4m3 for the plain / QuickGELU / GELU epilogues
-int dfd_gemm256p_f8_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st) { return try_persistent<Gemm256p, true>(a, c_dtype, epi, st); }
+// f8: e4m3 operands on the block-scaled matrix cores; cf8: C as e4m3 (the plain / QuickGELU / GELU epilogues)
+int dfd_gemm256p_launch(const GemmPlan& p, GemmArgs& a, bool f8, bool cf8, hipStream_t st) { return launch_persistent<Gemm256p>(p, a, f8, cf8, st); }

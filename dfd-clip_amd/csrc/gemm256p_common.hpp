@@ -1,12 +1,13 @@
 // Pieces shared by the two persistent GEMM kernels (gemm256e.hip: ping-pong K loop, tried first; gemm256p.hip: the K
 // depths that one does not serve; each with a bf16 and an e4m3 form).  They differ in their K loops only.  Here: tile /
 // ring geometry, the tile order, counted vmcnt waits, buffer descriptors, THE per-tile epilogue (tile_epilogue) and the
-// host side (tile plan, eligibility, dispatch to an instantiation).  A K step is 128 BYTES of every operand row (64 bf16
-// or 128 fp8 elements), so the LDS ring, the LDS-DMA pieces and the XOR swizzle are the same for both element types.
+// host side (the planned launch of an instantiation; the plan itself is gemm_plan.hpp's).  A K step is 128 BYTES of every
+// operand row (64 bf16 or 128 fp8 elements), so the LDS ring, the LDS-DMA pieces and the XOR swizzle are the same for both
+// element types.
 #pragma once
 #include <type_traits>
 
-#include "gemm_args.hpp"
+#include "gemm_plan.hpp"
 
 #include "gelu.hpp"
 #include "gemm_blocked.hpp"
@@ -366,143 +367,33 @@ __device__ __forceinline__ int tile_epilogue(const GemmArgs& a, f32x4 (&acc)[RB]
   return stores;
 }
 
-// ---- host side: one tile plan, one eligibility check, one dispatch ------------------------------------------------------
-struct TilePlan {
-  int rows, tiles_m;  // tile height (224 / 256) and row panels
-  int64_t ntiles;
-  int grid;  // workgroups = min(CUs left to this launch, tiles); 0: no device
-};
 
-// spare_if_free: `spare_cus` is a request, not an order — honoured where the rounds of tiles (at the best height allowed)
-// stay the same.  force224: the epilogue only exists for 224-row tiles.
-inline TilePlan plan_tiles(int64_t M, int N, int spare_cus, bool spare_if_free, int tile_rows, bool f8, bool force224) {
-  const int n_cu = dfd_cu_count(), tiles_n = N / TN;
-  if (n_cu == 0) return TilePlan{0, 0, 0, 0};
-  int cus = n_cu - spare_cus;
-  cus = cus < n_cu / 2 ? n_cu / 2 : cus;
-  // tile height: the one with the least (rounds of tiles) x (cost of a tile).  A 224-row tile saves the MFMA and
-  // epilogue work of 32 rows but stages as many bytes as a 256-row one, and the loop is bound by that staging:
-  // measured on the four ViT-B/16 shapes it costs 0.97 of a full tile, so it wins only where it saves a whole
-  // round (M = 94,560: N = 768 needs 5 rounds either way -> 224; N = 2304 / 3072: 15 vs 14, 20 vs 18 -> 256)
-  auto cost = [&](int rows, int c) { return (double)((((M + rows - 1) / rows) * tiles_n + c - 1) / c) * (rows == 224 ? 0.97 : 1.0); };
-  if (spare_cus > 0 && spare_if_free) {
-    auto best = [&](int c) { return f8 ? cost(256, c) : force224 ? cost(224, c) : (cost(224, c) < cost(256, c) ? cost(224, c) : cost(256, c)); };
-    if (best(cus) > best(n_cu)) cus = n_cu;
+// ---- host side: the planned launch of kernel family L (Gemm256p / Gemm256e: `kernel`, `name`, and `run`, which launches
+// one instantiation).  Nothing is decided here: the plan (gemm_plan.hpp) names the epilogue and the tile height, and a
+// family instantiates exactly the forms gemm_serves lists for it.
+template <class L>
+int launch_persistent(const GemmPlan& p, GemmArgs& a, bool f8, bool cf8, hipStream_t st) {
+  if (p.epilogue == DFD_EPI_QKV_EXPORT || p.epilogue == DFD_EPI_RESIDUAL_POS) {
+    // row -> (frame, token), frame -> frame % T; RESIDUAL_POS rows have no CLS row
+    a.div_tokens = FastDiv::make((uint32_t)(p.epilogue == DFD_EPI_RESIDUAL_POS ? a.tokens - 1 : a.tokens));
+    a.div_frames = FastDiv::make((uint32_t)(a.frames_per_clip > 0 ? a.frames_per_clip : 1));
   }
-  const bool use224 = !f8 && (force224 || tile_rows == 224 || (tile_rows == 0 && cost(224, cus) < cost(256, cus)));
-  TilePlan p;
-  p.rows = use224 ? 224 : 256;
-  p.tiles_m = (int)((M + p.rows - 1) / p.rows);
-  p.ntiles = (int64_t)p.tiles_m * tiles_n;
-  p.grid = (int)(p.ntiles < cus ? p.ntiles : cus);
-  return p;
-}
-
-// Launch of kernel family L (Gemm256p / Gemm256e: `run` launches one instantiation, `prepare` may add arguments that
-// depend on the plan) at the planned tile height.
-template <class L, int EPI, bool F8, bool CF8>
-int launch_persistent(const GemmArgs& a_in, hipStream_t st) {
-  constexpr bool force224 = EPI == DFD_EPI_RESIDUAL_POS;
-  GemmArgs a = a_in;
-  const TilePlan p = plan_tiles(a.M, a.N, a.spare_cus, L::spare_if_free && a.spare_if_free, a.tile_rows, F8, force224);
-  if (p.grid == 0) {
-    dfd_set_error("dfd_gemm(%s): cannot query the device", L::name);
-    return DFD_ERR_LAUNCH;
-  }
-  L::prepare(a, st, p, F8);
-  const int tiles_n = a.N / TN;
-  if constexpr (F8) {
-    L::template run<EPI, 8, true, CF8>(p.grid, st, a, p.tiles_m, tiles_n);
-  } else {
-    if (p.rows == 224) L::template run<EPI, 7, false, false>(p.grid, st, a, p.tiles_m, tiles_n);
-    else if constexpr (!force224) L::template run<EPI, 8, false, false>(p.grid, st, a, p.tiles_m, tiles_n);
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    dfd_set_error("dfd_gemm(%s): launch failed: %s", L::name, hipGetErrorString(e));
-    return DFD_ERR_LAUNCH;
-  }
-  return DFD_OK;
-}
-
-// eligibility common to both kernels: 0 = fine, 1 = not served.  (Each adds its own rule for the K depth: L::depth_ok.)
-inline int check_persistent(const GemmArgs& a, int esz, int csz, int kstep) {
-  if (a.N % TN != 0 || a.K % kstep != 0 || (a.M < 1024 && !a.pair)) return 1;  // (one half of a c_fc -> c_proj pair: any M)
-  if ((a.lda * esz) % 16 != 0 || (a.ldw * esz) % 16 != 0 || (a.ldc * csz) % 16 != 0) return 1;
-  if ((reinterpret_cast<uintptr_t>(a.A) & 15) != 0 || (reinterpret_cast<uintptr_t>(a.W) & 15) != 0 || (reinterpret_cast<uintptr_t>(a.C) & 15) != 0) return 1;
-  if (a.bias && (reinterpret_cast<uintptr_t>(a.bias) & 15) != 0) return 1;
-  const int64_t lim = (int64_t)0xfffffff0;  // buffer descriptors carry 32-bit byte offsets
-  const int64_t Mr = a.pair ? (a.M + 15) & ~(int64_t)15 : a.M;  // a blocked matrix keeps whole groups of 16 rows
-  if (Mr * a.lda * esz > lim || (int64_t)a.N * a.ldw * esz > lim || Mr * a.ldc * csz > lim) return 1;
-  if ((int64_t)((a.M + 223) / 224) * (a.N / TN) > 0x3fffffff || a.M >= ((int64_t)1 << 31)) return 1;
-  // the fragment-blocked layout (gemm_blocked.hpp): bf16, whole 64-channel K tiles in every row group
-  if ((a.c_blocked || a.a_blocked) && (esz != 2 || csz != 2)) return 1;
-  if ((a.c_blocked && a.ldc % 64 != 0) || (a.a_blocked && a.lda % 64 != 0)) return 1;
-  return 0;
-}
-
-inline int check_export(const GemmArgs& a) {
-  if ((a.N / (3 - a.qkv_first)) % TN != 0) return 1;
-  if (a.pos && (reinterpret_cast<uintptr_t>(a.pos) & 15) != 0) return 1;
-  if (a.k_export && (a.M / a.tokens) * (a.tokens - 1) * (int64_t)(a.N / (3 - a.qkv_first)) * 2 > (int64_t)0xfffffff0) return 1;
-  return 0;
-}
-
-inline int check_residual_pos(const GemmArgs& a) {
-  if (a.tokens < 2 || a.M * (int64_t)(a.N >> 3) >= ((int64_t)1 << 32)) return 1;
-  if (a.pos && ((reinterpret_cast<uintptr_t>(a.pos) & 15) != 0 || a.frames_per_clip < 1)) return 1;
-  if (a.residual && (reinterpret_cast<uintptr_t>(a.residual) & 15) != 0) return 1;
-  return 0;
-}
-
-// (epi, c_dtype, F8) -> an instantiation of kernel family L, where L serves it: 0 = launched, <0 = error, 1 = shape /
-// epilogue not served.  fp8 operands: C bf16, or e4m3 for the plain / QuickGELU / GELU epilogues.
-// The shape / layout rules of kernel family L for a call, without launching anything: 0 = fine, 1 = not served.  The
-// first thing try_persistent asks, and what the host's plan of a c_fc -> c_proj pair asks for both halves (gemm.hip,
-// dfd_gemm_pair_plan), so that the plan cannot say yes to a call the launcher then refuses.
-template <class L, bool F8>
-int persistent_serves(const GemmArgs& a_in, int c_dtype, int epi) {
-  if (c_dtype != DFD_BF16 && !(F8 && c_dtype == DFD_FP8)) return 1;
-  const bool cf8 = c_dtype == DFD_FP8;
-  constexpr int esz = F8 ? 1 : 2, kstep = F8 ? 128 : TK;
-  if (F8 && (!a_in.col_scale || (reinterpret_cast<uintptr_t>(a_in.col_scale) & 15) != 0)) return 1;
-  if (check_persistent(a_in, esz, cf8 ? 1 : 2, kstep) || !L::depth_ok(a_in, esz, a_in.K / kstep, epi)) return 1;
-  if (!L::serves(epi, F8)) return 1;
-  // blocked C: the MLP's activation epilogues write it; blocked A: the plain epilogue reads it (L::blocked_layout)
-  if ((a_in.c_blocked || a_in.a_blocked) && !L::blocked_layout) return 1;
-  if (a_in.c_blocked && epi != DFD_EPI_BIAS_QUICKGELU && epi != DFD_EPI_BIAS_GELU) return 1;
-  if (a_in.a_blocked && epi != DFD_EPI_BIAS) return 1;
-  return 0;
-}
-
-template <class L, bool F8>
-int try_persistent(const GemmArgs& a_in, int c_dtype, int epi, hipStream_t st) {
-  if (persistent_serves<L, F8>(a_in, c_dtype, epi)) return 1;
-  const bool cf8 = c_dtype == DFD_FP8;
-  GemmArgs a = a_in;
   auto go = [&](auto epi_c) -> int {
     constexpr int EPI = decltype(epi_c)::value;
-    constexpr bool rows_to_frames = EPI == DFD_EPI_QKV_EXPORT || EPI == DFD_EPI_RESIDUAL_POS;
-    if constexpr (!L::serves(EPI, F8)) {
-      return 1;
-    } else {
-      if constexpr (EPI == DFD_EPI_QKV_EXPORT) {
-        if (check_export(a)) return 1;
+    if (f8) {  // e4m3 operands: 256-row tiles; C bf16, or e4m3 where no row maps to a frame
+      if constexpr (gemm_serves(L::kernel, EPI, true)) {
+        if constexpr (EPI != DFD_EPI_QKV_EXPORT) {
+          if (cf8) return L::template run<EPI, 8, true, true>(p, st, a);
+        }
+        return L::template run<EPI, 8, true, false>(p, st, a);
       }
-      if constexpr (EPI == DFD_EPI_RESIDUAL_POS) {
-        if (check_residual_pos(a)) return 1;
-      }
-      if constexpr (rows_to_frames) {  // row -> (frame, token), frame -> frame % T; RESIDUAL_POS rows have no CLS row
-        a.div_tokens = FastDiv::make((uint32_t)(EPI == DFD_EPI_RESIDUAL_POS ? a.tokens - 1 : a.tokens));
-        a.div_frames = FastDiv::make((uint32_t)(a.frames_per_clip > 0 ? a.frames_per_clip : 1));
-      }
-      if constexpr (F8 && !rows_to_frames) {
-        if (cf8) return launch_persistent<L, EPI, true, true>(a, st);
-      }
-      return cf8 ? 1 : launch_persistent<L, EPI, F8, false>(a, st);
+    } else if constexpr (gemm_serves(L::kernel, EPI, false)) {
+      if (p.tiles.rows == 224) return L::template run<EPI, 7, false, false>(p, st, a);
+      if constexpr (EPI != DFD_EPI_RESIDUAL_POS) return L::template run<EPI, 8, false, false>(p, st, a);  // (that epilogue only exists for 224-row tiles)
     }
+    return DFD_ERR_INVALID_ARG;  // not reached: the plan names no form a family lacks
   };
-  switch (epi) {
+  switch (p.epilogue) {
     case DFD_EPI_BIAS:
       return go(std::integral_constant<int, DFD_EPI_BIAS>{});
     case DFD_EPI_BIAS_QUICKGELU:
@@ -514,7 +405,7 @@ int try_persistent(const GemmArgs& a_in, int c_dtype, int epi, hipStream_t st) {
     case DFD_EPI_RESIDUAL_POS:
       return go(std::integral_constant<int, DFD_EPI_RESIDUAL_POS>{});
     default:
-      return 1;
+      return DFD_ERR_INVALID_ARG;
   }
 }
 

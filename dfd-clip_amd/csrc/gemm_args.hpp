@@ -1,6 +1,6 @@
 // Argument block shared by the GEMM kernels: gemm.hip (general shapes, 128-wide tiles), gemm256.hip (tuned bf16, one
 // workgroup per tile) and the two persistent kernels gemm256e.hip / gemm256p.hip (bf16 and e4m3 operands; their shared
-// epilogue, tile plan and dispatch are in gemm256p_common.hpp).
+// epilogue is in gemm256p_common.hpp).  Which kernel serves a call, and with which tiles: gemm_plan.hpp.
 #pragma once
 #include "dropout.hpp"
 
@@ -29,17 +29,9 @@ struct GemmArgs {
   // (blockIdx & 7), and the value each held when this launch was enqueued; NULL = tiles are dealt statically
   uint32_t* sched;
   uint32_t sched_base[8];
-  int no_dynamic;  // tests / A-B: 1 = keep the static order
+  int no_dynamic;  // (not read any more: GemmPlan::dynamic decides; kept so that the kernels' argument layout stays as it was)
   // gemm256e.hip, the c_fc -> c_proj pair (gemm_blocked.hpp): C is written / A is read in the fragment-blocked layout.
   // pair: the call is one half of such a pair (DFD_GEMM_C_BLOCKED / DFD_GEMM_A_BLOCKED) — gemm256e.hip serves it, at any
   // M, or it is an error; dfd_gemm_pair_set_variant(1) keeps `pair` and clears the other two (the row-major pair).
   int c_blocked, a_blocked, pair;
 };
-
-// tuned kernels: 0 = launched, <0 = error, 1 = shape / epilogue not eligible
-int dfd_gemm256_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st);      // gemm256.hip: one workgroup per tile
-int dfd_gemm256e_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st);     // gemm256e.hip: persistent, ping-pong K loop (tried first)
-int dfd_gemm256e_serves(const GemmArgs& a, int c_dtype, int epi);                   // ... would it serve the bf16 call? 1 = yes (no launch)
-int dfd_gemm256e_f8_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st);  // same kernel, e4m3 operands (dfd_gemm_fp8)
-int dfd_gemm256p_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st);     // gemm256p.hip: persistent, the K depths gemm256e does not serve
-int dfd_gemm256p_f8_try(const GemmArgs& a, int c_dtype, int epi, hipStream_t st);  // same kernel, e4m3 operands

@@ -176,8 +176,8 @@ int dfd_gemm_fp8(const void* A, int64_t lda, const void* W, int64_t ldw, void* C
                  const dfd_gemm_extra* extra, int64_t M, int N, int K, void* stream);
 
 /* Which kernel served this thread's last successful dfd_gemm: 257 = the persistent 256x256 kernel with the ping-pong
- * K loop (M >= 1024, N % 256 == 0, K % 128 == 0, K >= 384), 256 = the other tuned 256x256 bf16 kernels (K % 64 == 0,
- * K >= 128), 128 = the general 128x128 kernel, 0 = none yet.  For tests and profilers. */
+ * K loop, 256 = the other tuned 256x256 bf16 kernels, 128 = the general 128x128 kernel, 0 = none yet.  For tests and
+ * profilers; the rules that pick one and dfd_gemm_last_kernel, which tells the two 256s apart: dfdclip_hooks.h. */
 int dfd_gemm_last_path(void);
 
 /* Tests and A/B measurements: 0 (default) = every kernel eligible; 1 = skip the ping-pong kernel, so that the round-2

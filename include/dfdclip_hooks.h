@@ -62,6 +62,60 @@ int dfd_attention_plan(int dtype, int n_frames, int tokens, int heads, int64_t l
  * as it did before that kernel existed.  Per thread; returns the previous value. */
 int dfd_attention_set_variant(int variant);
 
+/* The kernels behind dfd_gemm and dfd_gemm_fp8 and the rule that picks one (gemm_plan in csrc/gemm_plan.hpp is the only
+ * code that knows it).  A K step is 128 bytes of an operand row: 64 bf16 or 128 e4m3 elements; steps = K / that.  "aligned":
+ * 16 bytes.  The first row that matches wins:
+ *   f32 operands                                                                   -> GENERAL (below)
+ *   PINGPONG, unless dfd_gemm_set_variant(1): bf16 or e4m3 operands; C bf16 (e4m3 operands, no QKV_EXPORT: or e4m3);
+ *     M >= 1024 (one half of a c_fc -> c_proj pair: any M); N % 256 == 0; steps even and >= 6 (RESIDUAL_POS: or 4);
+ *     ldw a multiple of 128 bytes, lda and ldc of 16; A, W, C, bias (e4m3: and col_scale) aligned; the bytes of A, W and C
+ *     (M rounded up to 16 in a pair) each <= 0xfffffff0; ceil(M / 224) * N / 256 <= 0x3fffffff; M < 2^31;
+ *     BIAS, BIAS_QUICKGELU, BIAS_GELU, QKV_EXPORT, and for bf16 RESIDUAL_POS;
+ *     DFD_GEMM_C_BLOCKED: bf16, ldc % 64 == 0, BIAS_QUICKGELU / BIAS_GELU; DFD_GEMM_A_BLOCKED: bf16, lda % 64 == 0, BIAS;
+ *     QKV_EXPORT with export buffers (without them it is BIAS here): the column block N / (3 - qkv_first) a multiple of
+ *     256, pos aligned, the export's bytes <= 0xfffffff0; RESIDUAL_POS: M * (N / 8) < 2^32, pos and residual aligned
+ *   PERSISTENT: the same rules with steps >= 2 and ldw a multiple of 16 bytes; BIAS, BIAS_QUICKGELU, QKV_EXPORT, and for
+ *     e4m3 BIAS_GELU; no blocked layout
+ *   a call with DFD_GEMM_C_BLOCKED / _A_BLOCKED that PINGPONG does not serve, and an e4m3 call neither serves -> refused
+ *   TILE: bf16 operands; M >= 1024; N % 256 == 0; K % 64 == 0, K >= 128; lda % 8 == ldw % 8 == ldc % 4 == 0; C and bias
+ *     aligned; ceil(M / 256) * N / 256 <= 2^31 - 1; M < 2^31; BIAS, BIAS_QUICKGELU, QKV_EXPORT (column block a multiple of
+ *     256, pos aligned) with either C; BIAS_RESIDUAL and PATCH_EMBED (pos, cls aligned) with f32 C; RESIDUAL_POS with bf16
+ *     C, ldc % 8 == 0, pos and residual aligned
+ *   GENERAL: everything else dfd_gemm accepts (BIAS_RESIDUAL, PATCH_EMBED: f32 C, else refused)
+ * Launches: GENERAL grid (ceil(N / 128), ceil(M / 128)), block 256; TILE grid ceil(M / 256) * N / 256, block 512; the
+ * persistent two: block 512, tiles of tile_rows x 256, grid = min(tiles, CUs), CUs = max(n_cu - spare_cus, n_cu / 2).
+ * tile_rows: e4m3 256; RESIDUAL_POS 224; DFD_GEMM_TILE_BLOCKS 7 / 8 forced; else 224 where 0.97 * rounds(224) <
+ * rounds(256), rounds(r) = ceil(ceil(M / r) * N / 256 / CUs).  DFD_GEMM_SPARE_IF_FREE (PINGPONG only): CUs = n_cu where the
+ * cheaper height's cost on n_cu is below that on CUs.  dynamic: PINGPONG, bf16, steps >= 6, dfd_gemm_set_variant(3). */
+enum { DFD_GEMM_GENERAL = 1, /* gemm.hip: 128x128 tiles, any shape */
+       DFD_GEMM_TILE = 2,    /* gemm256.hip: one workgroup per 256x256 tile */
+       DFD_GEMM_PERSISTENT = 3, /* gemm256p.hip: persistent, every K depth from two steps */
+       DFD_GEMM_PINGPONG = 4 /* gemm256e.hip: persistent, ping-pong K loop */ };
+/* one bit per pointer of a call, for dfd_gemm_plan's `has` and `misaligned` */
+enum { DFD_GEMM_PTR_A = 1, DFD_GEMM_PTR_W = 2, DFD_GEMM_PTR_C = 4, DFD_GEMM_PTR_BIAS = 8, DFD_GEMM_PTR_POS = 16, DFD_GEMM_PTR_CLS = 32,
+       DFD_GEMM_PTR_RESIDUAL = 64, DFD_GEMM_PTR_COL_SCALE = 128, DFD_GEMM_PTR_EXPORT = 256 /* k_export and v_export */ };
+typedef struct {
+  int32_t kernel;             /* DFD_GEMM_* */
+  int32_t epilogue;           /* of the instantiation: QKV_EXPORT without export buffers is BIAS on the persistent kernels */
+  int32_t tile_rows, tiles_m; /* tile height and row panels */
+  int64_t ntiles;
+  uint32_t grid, grid_y, block;
+  int32_t c_blocked, a_blocked; /* the layout flags in force (dfd_gemm_pair_set_variant(1) clears them) */
+  int32_t dynamic;              /* 1 = the dynamic tile hand-out may be prepared */
+} dfd_gemm_plan_t;
+
+/* The kernel (DFD_GEMM_*) of this thread's last successful dfd_gemm or dfd_gemm_fp8 that launched one; 0 = none yet.
+ * dfd_gemm_last_path (dfdclip.h) reports dfd_gemm's share of the same record as 128 / 256 / 257. */
+int dfd_gemm_last_kernel(void);
+/* What dfd_gemm (ab_dtype DFD_F32 / DFD_BF16) or dfd_gemm_fp8 (DFD_FP8) would do with a call under the thread's current
+ * variants: returns the kernel (0 for M == 0: nothing is launched) and fills *out (may be NULL), or returns -1 with
+ * dfd_last_error() in the words of the entry point.  flags: dfd_gemm_extra.flags; has: which of DFD_GEMM_PTR_EXPORT, _POS,
+ * _RESIDUAL the call carries (the others are taken as present); misaligned: the pointers that are not 16-byte aligned, 0 =
+ * none.  No pointer is involved and, with n_cu > 0, no device (n_cu <= 0: the current device's count). */
+int dfd_gemm_plan(int ab_dtype, int c_dtype, int epilogue, int64_t M, int N, int K, int64_t lda, int64_t ldw, int64_t ldc,
+                  uint32_t flags, int tokens, int frames_per_clip, int qkv_first, unsigned has, unsigned misaligned, int n_cu,
+                  dfd_gemm_plan_t* out);
+
 /* The c_fc -> c_proj pair of the encoder's MLP (DFD_GEMM_C_BLOCKED / DFD_GEMM_A_BLOCKED).  0 (default) = the pair keeps
  * the intermediate fragment-blocked where dfd_gemm_pair_plan says so; 1 = row-major everywhere: the plan answers 0 and a
  * call that carries one of the bits runs on the same kernel with a row-major C / A (the bits then only waive the

@@ -241,3 +241,261 @@ def test_cpu_tensors_fail_loudly(lib):
 def test_missing_library_fails_loudly(tmp_path):
     with pytest.raises(capi.DfdError):
         capi.load_library(str(tmp_path / "nope.so"))
+
+
+def test_gemm_plan_table(lib):
+    """The selection table of include/dfdclip_hooks.h (gemm_plan in csrc/gemm_plan.hpp), through dfd_gemm_plan: every row on
+    both sides of every edge, with kernel, effective epilogue, tile height, row panels, grid and block.  No device: n_cu is
+    given.  The expectations come from the table's words, modelled below, never from the library."""
+    c = capi
+    F, B, E = c.F32, c.BF16, c.FP8
+    GEN, TILE, PERS, PING = c.GEMM_GENERAL, c.GEMM_TILE, c.GEMM_PERSISTENT, c.GEMM_PINGPONG
+    BIAS, QGELU, BRES, PATCH, QKV, RPOS, GELU = (c.EPI_BIAS, c.EPI_BIAS_QUICKGELU, c.EPI_BIAS_RESIDUAL, c.EPI_PATCH_EMBED, c.EPI_QKV_EXPORT,
+                                                  c.EPI_RESIDUAL_POS, c.EPI_BIAS_GELU)
+    EXPORT, POS, RES = c.GEMM_PTR_EXPORT, c.GEMM_PTR_POS, c.GEMM_PTR_RESIDUAL
+    LIM = 0xfffffff0
+    ceil = lambda a, b: -(-a // b)
+
+    def plan(ab, cd, epi, M, N, K, variant=0, pair=0, **kw):
+        assert c.gemm_set_variant(variant) == 0 and c.gemm_pair_set_variant(pair) == 0
+        kw.setdefault("frames_per_clip", 3)
+        try:
+            p = c.gemm_plan(ab, cd, epi, M, N, K, **kw)
+        finally:
+            c.gemm_set_variant(0)
+            c.gemm_pair_set_variant(0)
+        assert p.ntiles == p.tiles_m * (ceil(N, 128) if p.kernel == GEN else N // 256)
+        return p.kernel, p.epilogue, p.tile_rows, p.tiles_m, p.grid, p.grid_y, p.block
+
+    def refused(*a, match, **kw):
+        with pytest.raises(capi.DfdError, match=match):
+            plan(*a, **kw)
+
+    # the table's launch rows
+    general = lambda M, N, epi=BIAS: (GEN, epi, 128, ceil(M, 128), ceil(N, 128), ceil(M, 128), 256)
+    tile = lambda M, N, epi=BIAS: (TILE, epi, 256, ceil(M, 256), ceil(M, 256) * (N // 256), 1, 512)
+    rounds = lambda M, N, rows, cus: ceil(ceil(M, rows) * (N // 256), cus)
+    height = lambda M, N, cus: 224 if 0.97 * rounds(M, N, 224, cus) < rounds(M, N, 256, cus) else 256
+
+    def persistent(kernel, M, N, epi=BIAS, rows=None, cus=256):
+        rows = rows or height(M, N, cus)
+        return (kernel, epi, rows, ceil(M, rows), min(ceil(M, rows) * (N // 256), cus), 1, 512)
+
+    ping = lambda *a, **kw: persistent(PING, *a, **kw)
+    pers = lambda *a, **kw: persistent(PERS, *a, **kw)
+
+    # ---- bf16 operands: M, N, K edges under variants 0 / 1 / 3, bf16 and f32 C -------------------------------------------
+    Ks = (64, 96, 128, 192, 256, 320, 384, 512, 640, 768)
+    for M in (1023, 1024):
+        for N in (255, 256, 257, 512):
+            for K in Ks:
+                for v in (0, 1, 3):
+                    tuned = M >= 1024 and N % 256 == 0 and K % 64 == 0
+                    steps = K // 64
+                    if tuned and v != 1 and steps % 2 == 0 and steps >= 6:
+                        want = ping(M, N)
+                    elif tuned and steps >= 2:
+                        want = pers(M, N)
+                    else:  # (with a bf16 C whatever the tile kernel serves a persistent kernel serves first)
+                        want = general(M, N)
+                    assert plan(B, B, BIAS, M, N, K, variant=v) == want, (M, N, K, v)
+                    # an f32 C: the one-workgroup-per-tile kernel from K = 128, K % 64 == 0
+                    assert plan(B, F, BIAS, M, N, K, variant=v) == (tile(M, N) if tuned and K >= 128 else general(M, N)), (M, N, K, v)
+                    # f32 operands: the general kernel whatever the shape
+                    assert plan(F, F, BIAS, M, N, K, variant=v) == general(M, N)
+                    # RESIDUAL_POS: 224-row tiles on the ping-pong kernel, also at 4 steps; never the round-2 persistent kernel
+                    if tuned and v != 1 and steps % 2 == 0 and (steps >= 6 or steps == 4):
+                        want = ping(M, N, RPOS, rows=224)
+                    else:
+                        want = tile(M, N, RPOS) if tuned and K >= 128 else general(M, N, RPOS)
+                    assert plan(B, B, RPOS, M, N, K, variant=v, tokens=17, has=POS | RES) == want, (M, N, K, v)
+    # the dynamic hand-out: ping-pong, bf16, six steps and more, variant 3 only
+    dyn = lambda v, K, epi=BIAS, ab=B: (c.gemm_set_variant(v), c.gemm_plan(ab, B, epi, 1024, 256, K, tokens=17).dynamic, c.gemm_set_variant(0))[1]
+    assert (dyn(3, 384), dyn(0, 384), dyn(3, 320), dyn(3, 256, RPOS), dyn(3, 384, RPOS), dyn(3, 768, ab=E)) == (1, 0, 0, 0, 1, 0)
+    # W rows that are no 128-byte multiple: the ping-pong kernel declines, the persistent one serves (dfd_gemm_last_path: 256)
+    assert plan(B, B, BIAS, 1024, 768, 768, ldw=768 + 8) == pers(1024, 768) and plan(B, B, BIAS, 1024, 768, 768, ldw=768 + 64) == ping(1024, 768)
+    # leading dimensions: 16-byte rows for the persistent kernels; the tile kernel takes ldc % 4; the entry point refuses lda % 8
+    assert plan(B, B, BIAS, 1024, 256, 384, ldc=256 + 8) == ping(1024, 256) and plan(B, B, BIAS, 1024, 256, 384, ldc=256 + 4) == tile(1024, 256)
+    assert plan(B, B, BIAS, 1024, 256, 384, ldc=256 + 2) == general(1024, 256)
+    refused(B, B, BIAS, 1024, 256, 384, lda=384 + 4, match="dfd_gemm: lda=388 ldw=384 must be >= K and 16-byte multiples")
+    # one misaligned pointer in turn
+    every = EXPORT | POS | RES
+    for bit in (c.GEMM_PTR_A, c.GEMM_PTR_W):
+        refused(B, B, BIAS, 1024, 768, 384, misaligned=bit, match="dfd_gemm: A and W must be 16-byte aligned")
+    for bit in (c.GEMM_PTR_C, c.GEMM_PTR_BIAS):
+        assert plan(B, B, BIAS, 1024, 768, 384, misaligned=bit) == general(1024, 768)
+        assert plan(B, F, BIAS, 1024, 768, 384, misaligned=bit) == general(1024, 768)
+    for bit in (POS, c.GEMM_PTR_CLS, RES, c.GEMM_PTR_COL_SCALE, EXPORT):  # pointers the plain epilogue does not read
+        assert plan(B, B, BIAS, 1024, 768, 384, has=every, misaligned=bit) == ping(1024, 768)
+    assert plan(B, B, QKV, 1024, 768, 384, tokens=2, has=every, misaligned=POS) == general(1024, 768, QKV)
+    assert plan(B, B, QKV, 1024, 768, 384, tokens=2, has=EXPORT, misaligned=POS) == ping(1024, 768, QKV)  # no pos: nothing to misalign
+    assert plan(B, B, RPOS, 1024, 768, 384, tokens=2, has=every, misaligned=RES) == general(1024, 768, RPOS)
+    assert plan(B, B, RPOS, 1024, 768, 384, tokens=2, has=every, misaligned=POS) == general(1024, 768, RPOS)
+    assert plan(B, F, PATCH, 1024, 768, 384, tokens=3, has=POS, misaligned=c.GEMM_PTR_CLS) == general(1024, 768, PATCH)
+    refused(E, B, BIAS, 1024, 768, 768, misaligned=c.GEMM_PTR_COL_SCALE, match="dfd_gemm_fp8: call not served: col_scale")
+
+    # ---- epilogues, bf16 and f32 C, at a ping-pong depth (6 steps) and at one only the round-2 kernels serve (5) ---------
+    M, N = 1024, 768
+    for K, p16 in ((384, ping), (320, pers)):
+        assert plan(B, B, BIAS, M, N, K) == p16(M, N) and plan(B, B, QGELU, M, N, K) == p16(M, N, QGELU)
+        assert plan(B, B, QKV, M, N, K, tokens=2, has=EXPORT) == p16(M, N, QKV)
+        assert plan(B, B, QKV, M, N, K, tokens=2, has=EXPORT, qkv_first=1) == general(M, N, QKV)  # N / 2 = 384: no whole tiles per block
+        assert plan(B, B, QKV, M, 512, K, tokens=2, has=EXPORT, qkv_first=1) == p16(M, 512, QKV)
+        assert plan(B, B, QKV, M, N, K, tokens=2) == p16(M, N, BIAS), "no export buffers: a plain biased store"
+        for epi in (BIAS, QGELU):
+            assert plan(B, F, epi, M, N, K) == tile(M, N, epi)
+        assert plan(B, F, QKV, M, N, K, tokens=2) == tile(M, N, QKV) and plan(B, F, QKV, M, N, K, tokens=2, has=EXPORT) == tile(M, N, QKV)
+        assert plan(B, F, BRES, M, N, K) == tile(M, N, BRES) and plan(B, F, PATCH, M, N, K, tokens=3, has=POS) == tile(M, N, PATCH)
+        assert plan(B, F, RPOS, M, N, K, tokens=17) == general(M, N, RPOS) and plan(B, F, GELU, M, N, K) == general(M, N, GELU)
+        refused(B, B, BRES, M, N, K, match="dfd_gemm: call not served: the epilogue needs an f32 C")
+        refused(B, B, PATCH, M, N, K, tokens=3, has=POS, match="dfd_gemm: PATCH_EMBED writes an f32 token matrix")
+        refused(B, B, 7, M, N, K, match="dfd_gemm: call not served: unknown epilogue")
+    # BIAS_GELU with bf16 operands: the ping-pong kernel or the general one
+    assert plan(B, B, GELU, M, N, 384) == ping(M, N, GELU) and plan(B, B, GELU, M, N, 320) == general(M, N, GELU)
+    assert plan(B, B, GELU, M, N, 384, variant=1) == general(M, N, GELU)
+    # RESIDUAL_POS: 224 rows whatever is asked; the tile kernel needs ldc % 8
+    assert plan(B, B, RPOS, M, N, 384, tokens=17, flags=8 << 16) == ping(M, N, RPOS, rows=224)
+    assert plan(B, B, RPOS, M, N, 320, tokens=17) == tile(M, N, RPOS) and plan(B, B, RPOS, M, N, 320, tokens=17, ldc=N + 4) == general(M, N, RPOS)
+    # f32 operands: every epilogue on the general kernel
+    for epi, kw in ((BIAS, {}), (QGELU, {}), (GELU, {}), (BRES, {}), (QKV, dict(tokens=2, has=EXPORT)), (RPOS, dict(tokens=17)), (PATCH, dict(tokens=3, has=POS))):
+        assert plan(F, F, epi, M, N, 384, **kw) == general(M, N, epi)
+    refused(F, B, BIAS, M, N, 384, match="dfd_gemm: f32 operands with bf16 output unsupported")
+
+    # ---- e4m3 operands: a step is 128 elements.  K = 128: one step, refused; 256 and 512: two and four steps, the round-2
+    # persistent kernel (the ping-pong loop starts at six); 768 and 1024: six and eight, the ping-pong kernel.  256-row tiles.
+    M, N = 1024, 768
+    for cd in (B, E):
+        refused(E, cd, BIAS, M, N, 128, match="dfd_gemm_fp8: call not served: K is less than two 128-byte steps")
+        for K, kernel in ((256, PERS), (512, PERS), (768, PING), (1024, PING)):
+            for epi in (BIAS, QGELU, GELU):
+                assert plan(E, cd, epi, M, N, K) == persistent(kernel, M, N, epi, rows=256), (cd, K, epi)
+                assert plan(E, cd, epi, M, N, K, variant=1) == pers(M, N, epi, rows=256)
+                assert plan(E, cd, epi, M, N, K, flags=7 << 16) == persistent(kernel, M, N, epi, rows=256), "no 224-row fp8 tiles"
+        refused(E, cd, RPOS, M, N, 768, tokens=17, match="dfd_gemm_fp8: epilogue 5 not served")
+    assert plan(E, B, QKV, M, N, 768, tokens=2, has=EXPORT) == ping(M, N, QKV, rows=256) and plan(E, B, QKV, M, N, 512, tokens=2, has=EXPORT) == pers(M, N, QKV, rows=256)
+    refused(E, E, QKV, M, N, 768, tokens=2, match="dfd_gemm_fp8: fp8 output needs")
+    refused(E, F, BIAS, M, N, 768, match="dfd_gemm_fp8: c_dtype=0")
+    refused(E, B, BIAS, 1023, N, 768, match=r"dfd_gemm_fp8: call not served: M < 1024 \(epilogue 0, M=1023 N=768 K=768\)")
+    refused(E, B, BIAS, M, 255, 768, match="dfd_gemm_fp8: call not served: N % 256 != 0")
+    refused(E, B, BIAS, M, N, 768 + 64, match="dfd_gemm_fp8: call not served: a row of K is not a whole number of 128-byte steps")
+    # what the package restates as constants: the row threshold of the fp8 path and the widths it is built for
+    assert c.FP8_MIN_ROWS == 1024
+    assert plan(E, B, BIAS, c.FP8_MIN_ROWS, 768, 768)[0] == PING
+    refused(E, B, BIAS, c.FP8_MIN_ROWS - 1, 768, 768, match="not served")
+    from dfd_clip_amd.dinov2 import ARCHS
+    tiny, base = ARCHS["dino_tiny"][2], ARCHS["dinov2_vitb14"][2]
+    assert (tiny, base) == (128, 768) and tiny % 256 != 0 and base % 256 == 0  # (dinov2.py refuses fp8 by width % 256)
+    refused(E, B, BIAS, 4096, 3 * tiny, tiny, match="not served")
+    refused(E, B, BIAS, 4096, tiny, 4 * tiny, match="not served")
+    assert plan(E, B, BIAS, 4096, 3 * base, base)[0] == PING and plan(E, B, GELU, 4096, 4 * base, base)[0] == PING
+
+    # ---- the c_fc -> c_proj pair: this kernel at any M, or an error; pair variant 1 keeps the kernel and clears the layout --
+    CB, AB = c.GEMM_C_BLOCKED, c.GEMM_A_BLOCKED
+    D, H = 768, 3072
+
+    def flags_in_force(epi, N, K, flag, M, pv, **kw):
+        assert c.gemm_pair_set_variant(pv) == 0
+        try:
+            p = c.gemm_plan(B, B, epi, M, N, K, flags=flag, **kw)
+            return p.kernel, p.c_blocked, p.a_blocked, bool(c.gemm_pair_plan(M, D, H))
+        finally:
+            c.gemm_pair_set_variant(0)
+
+    for M in (32, 1023, 1024):
+        for pv in (0, 1, 2):
+            fc = flags_in_force(QGELU, H, D, CB, M, pv)
+            pr = flags_in_force(BIAS, D, H, AB, M, pv)
+            assert fc[:3] == (PING, int(pv != 1), 0) and pr[:3] == (PING, 0, int(pv != 1)), (M, pv, fc, pr)
+            # the pair's plan: both halves planned blocked, plus the policy of 1024 rows (variant 2 waives it)
+            assert fc[3] == pr[3] == (fc[1] == 1 and pr[2] == 1 and (M >= 1024 or pv == 2)), (M, pv)
+            assert plan(B, B, QGELU, M, H, D, flags=CB, pair=pv) == ping(M, H, QGELU) and plan(B, B, BIAS, M, D, H, flags=AB, pair=pv) == ping(M, D)
+            assert flags_in_force(GELU, H, D, CB, M, pv)[:3] == fc[:3]
+    pair_words = "dfd_gemm: DFD_GEMM_C_BLOCKED / DFD_GEMM_A_BLOCKED: the ping-pong kernel does not serve this call: "
+    refused(B, B, QGELU, 1024, H, D, flags=CB, ldc=H + 8, match=pair_words + "the leading dimension of a fragment-blocked matrix")
+    refused(B, B, BIAS, 1024, D, H, flags=AB, lda=H + 8, match=pair_words + r".*\(epilogue 0, M=1024 N=768 K=3072\)")
+    assert plan(B, B, QGELU, 1024, H, D, flags=CB, ldc=H + 8, pair=1) == ping(1024, H, QGELU), "row-major: any 16-byte ldc"
+    assert plan(B, B, QGELU, 1024, H, D, flags=CB, ldc=H + 64) == ping(1024, H, QGELU)
+    refused(B, B, BIAS, 1024, H, D, flags=CB, match=pair_words + "DFD_GEMM_C_BLOCKED needs BIAS_QUICKGELU or BIAS_GELU")
+    refused(B, B, QGELU, 1024, D, H, flags=AB, match=pair_words + "DFD_GEMM_A_BLOCKED needs BIAS")
+    refused(B, B, QGELU, 1024, H, D, flags=CB, variant=1, match=pair_words + r"dfd_gemm_set_variant\(1\) skips the ping-pong kernel")
+    refused(B, B, QGELU, 32, 512, 128, flags=CB, match=pair_words + "the ping-pong K loop needs")
+    refused(B, F, QGELU, 1024, H, D, flags=CB, match=pair_words + "C must be bf16")
+    refused(E, B, QGELU, 1024, H, D, flags=CB, match="dfd_gemm_fp8: DFD_GEMM_C_BLOCKED / DFD_GEMM_A_BLOCKED: .*the fragment-blocked layout is bf16")
+    assert c.gemm_set_variant(1) == 0 and not c.gemm_pair_plan(94560, D, H) and c.gemm_set_variant(0) == 1
+
+    # ---- the tile plan on 256 compute units (ViT-B/16: 480 frames of 197 tokens) -------------------------------------------
+    M = 94560
+    assert plan(B, B, BIAS, M, 768, 768) == (PING, BIAS, 224, 423, 256, 1, 512)      # 5 rounds either way: the cheaper tile
+    assert plan(B, B, BIAS, M, 2304, 768) == (PING, BIAS, 256, 370, 256, 1, 512)     # 15 rounds of 224 rows against 14
+    assert plan(B, B, QGELU, M, 3072, 768) == (PING, QGELU, 256, 370, 256, 1, 512)   # 20 against 18
+    assert (rounds(M, 768, 224, 256), rounds(M, 768, 256, 256), rounds(M, 2304, 224, 256), rounds(M, 2304, 256, 256)) == (5, 5, 15, 14)
+    assert (rounds(M, 3072, 224, 256), rounds(M, 3072, 256, 256)) == (20, 18)
+    assert plan(B, B, BIAS, M, 2304, 768, flags=7 << 16) == ping(M, 2304, rows=224) and plan(B, B, BIAS, M, 768, 768, flags=8 << 16) == ping(M, 768, rows=256)
+    refused(B, B, BIAS, M, 768, 768, flags=5 << 16, match="dfd_gemm: tile blocks must be 0, 7 or 8")
+    for kernel, K in ((PING, 768), (PERS, 320)):
+        for spare, cus in ((32, 224), (100, 156), (200, 128)):  # binding, floored at half the chip
+            for N in (768, 2304):
+                assert plan(B, B, BIAS, M, N, K, flags=spare << 8) == persistent(kernel, M, N, cus=cus), (kernel, spare, N)
+    # DFD_GEMM_SPARE_IF_FREE: honoured where the cheaper height costs no more on the CUs left than on all of them (50,000 rows
+    # of N = 768: three rounds of 224-row tiles on 224 CUs as on 256), else every CU (94,560 rows: five rounds of 256-row tiles
+    # on 224 CUs, five cheaper ones of 224 rows on 256); the round-2 persistent kernel takes the request as given
+    cost = lambda M, N, cus: min(0.97 * rounds(M, N, 224, cus), rounds(M, N, 256, cus))
+    assert cost(50000, 768, 224) == cost(50000, 768, 256) == 0.97 * 3 and (cost(M, 768, 224), cost(M, 768, 256)) == (5, 0.97 * 5)
+    assert cost(M, 2304, 224) > cost(M, 2304, 256)
+    sif = (32 << 8) | c.GEMM_SPARE_IF_FREE
+    assert plan(B, B, BIAS, 50000, 768, 3072, flags=sif) == ping(50000, 768, cus=224) == (PING, BIAS, 224, 224, 224, 1, 512)
+    assert plan(B, B, BIAS, M, 768, 3072, flags=sif) == ping(M, 768, cus=256) == (PING, BIAS, 224, 423, 256, 1, 512)
+    assert plan(B, B, BIAS, M, 2304, 768, flags=sif) == ping(M, 2304, cus=256)
+    assert plan(B, B, BIAS, M, 2304, 320, flags=sif) == pers(M, 2304, cus=224)
+    assert plan(E, B, BIAS, M, 2304, 768, flags=sif) == ping(M, 2304, rows=256, cus=256) and plan(E, B, BIAS, M, 2304, 768, flags=32 << 8) == ping(M, 2304, rows=256, cus=224)
+    # fewer tiles than CUs; a small chip
+    assert plan(B, B, BIAS, 1024, 256, 384) == (PING, BIAS, 224, 5, 5, 1, 512) and plan(B, B, BIAS, 1024, 256, 384, flags=8 << 16) == (PING, BIAS, 256, 4, 4, 1, 512)
+    assert plan(B, B, BIAS, M, 768, 768, n_cu=8) == ping(M, 768, cus=8) and ping(M, 768, cus=8)[4] == 8
+    assert plan(B, B, BIAS, M, 768, 768, n_cu=8, flags=6 << 8) == ping(M, 768, cus=4)
+
+    # ---- 32-bit extents: the first M at which a rule trips, and the one before --------------------------------------------
+    # (the persistent kernels address A, W and C through buffer descriptors; past them the tile kernel, which has no such
+    # limit, serves the call.  The export's and RESIDUAL_POS's own limits cannot bind before C's: C is the larger matrix.)
+    N, K = 256, 384
+    for lda, ldc in ((K, N), (K, N + 4096), (K + 4096, N)):
+        first = min(LIM // (lda * 2), LIM // (ldc * 2)) + 1
+        assert max((first - 1) * lda, (first - 1) * ldc) * 2 <= LIM < max(first * lda, first * ldc) * 2
+        assert plan(B, B, BIAS, first - 1, N, K, lda=lda, ldc=ldc) == ping(first - 1, N)
+        assert plan(B, B, BIAS, first, N, K, lda=lda, ldc=ldc) == tile(first, N)
+        assert plan(B, B, BIAS, first, N, 320, lda=lda if lda > K else 320, ldc=ldc)[0] == (TILE if lda == K + 4096 or ldc > N else PERS)
+    first = LIM // 768 + 1  # e4m3: one byte per element, and no other kernel
+    assert plan(E, B, BIAS, first - 1, N, 768) == ping(first - 1, N, rows=256)
+    refused(E, B, BIAS, first, N, 768, match="dfd_gemm_fp8: call not served: A, W or C exceeds the 32-bit byte offsets")
+    ldw = (LIM // (N * 2) // 64 + 1) * 64  # W: N rows of ldw elements
+    assert N * (ldw - 64) * 2 <= LIM < N * ldw * 2
+    assert plan(B, B, BIAS, 1024, N, K, ldw=ldw - 64) == ping(1024, N) and plan(B, B, BIAS, 1024, N, K, ldw=ldw) == tile(1024, N)
+    # a blocked matrix keeps whole groups of 16 rows: the rounded-up M counts
+    first = (LIM // (D * 2)) // 16 * 16 + 1
+    assert (first - 1) * D * 2 <= LIM < (first + 15) * D * 2 and first * D * 2 <= LIM
+    assert plan(B, B, BIAS, first - 1, 256, D, flags=AB) == ping(first - 1, 256) and plan(B, B, BIAS, first, 256, D) == ping(first, 256)
+    refused(B, B, BIAS, first, 256, D, flags=AB, match=pair_words + "A, W or C exceeds")
+    # the tile kernel: rows below 2^31, tiles within 2^31 - 1
+    assert plan(B, F, BIAS, (1 << 31) - 1, 256, 128) == tile((1 << 31) - 1, 256) and plan(B, F, BIAS, 1 << 31, 256, 128) == general(1 << 31, 256)
+    wide = 256 * 257
+    first = 256 * ((2 ** 31 - 1) // 257) + 1
+    assert ceil(first - 1, 256) * 257 <= 2 ** 31 - 1 < ceil(first, 256) * 257
+    assert plan(B, F, BIAS, first - 1, wide, 128) == tile(first - 1, wide) and plan(B, F, BIAS, first, wide, 128) == general(first, wide)
+
+    # ---- nothing to launch; the guarded harness's padded rows take the dense call's kernel ---------------------------------
+    assert plan(B, B, BIAS, 0, 768, 768) == (0, BIAS, 0, 0, 0, 0, 0)
+    for K in (192, 320, 384, 768):
+        assert plan(B, B, QGELU, 2893, 768, K, lda=K + 8, ldw=K + 64, ldc=768 + 8) == plan(B, B, QGELU, 2893, 768, K)
+
+    # ---- a refused call leaves the record of the last kernel alone, and the entry points refuse in the hook's words -------
+    p = 1 << 12
+    kernel_before, path_before = lib.dfd_gemm_last_kernel(), lib.dfd_gemm_last_path()
+    ex = capi.GemmExtra(None, None, None, None, 0, 0, None, 0, None, 0, 0.0, CB)
+    assert lib.dfd_gemm(p, D, p, D, B, p, H + 8, B, p, QGELU, ex, 1024, H, D, None) == -1
+    err = lib.dfd_last_error()
+    refused(B, B, QGELU, 1024, H, D, flags=CB, ldc=H + 8, match=re.escape(err.decode()))
+    assert lib.dfd_gemm_fp8(p, 768, p, 768, p, 768, B, p, p, 0.0, BIAS, None, 1023, 768, 768, None) == -1
+    assert lib.dfd_last_error() == b"dfd_gemm_fp8: call not served: M < 1024 (epilogue 0, M=1023 N=768 K=768)"
+    assert lib.dfd_gemm(p, 48, p, 48, B, p, 8, B, None, BIAS, None, 4, 8, 48, None) == -1 and b"multiple of 32" in lib.dfd_last_error()
+    assert lib.dfd_gemm(p, 64, p, 64, B, p, 8, B, None, BRES, None, 4, 8, 64, None) == -1 and b"needs an f32 C" in lib.dfd_last_error()
+    assert lib.dfd_gemm(p, 64, p, 64, B, p, 8, B, None, BIAS, None, 0, 8, 64, None) == 0  # M = 0: accepted, nothing launched
+    assert (lib.dfd_gemm_last_kernel(), lib.dfd_gemm_last_path()) == (kernel_before, path_before)

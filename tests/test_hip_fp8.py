@@ -107,21 +107,23 @@ def test_gemm_fp8_pingpong_equals_persistent(capi, M, N, K):
     cs = (torch.rand(N, generator=g) * 0.02 + 0.001).cuda()
     bias = (torch.randn(N, generator=g) * 0.1).cuda()
 
-    def run():
+    def run(kernel):
         c = torch.full((M, N), float("nan"), device="cuda", dtype=torch.bfloat16)
         capi.gemm_fp8(a8, w8, c, cs, bias, capi.EPI_BIAS_QUICKGELU)
+        assert capi.gemm_last_kernel() == kernel, "bf16 output"
         c8 = torch.zeros(M, N, device="cuda", dtype=torch.uint8)
         capi.gemm_fp8(a8, w8, c8, cs, bias, capi.EPI_BIAS, out_inv_scale=0.5)
+        assert capi.gemm_last_kernel() == kernel, "e4m3 output"
         return c, c8
 
     capi.gemm_set_variant(1)
     try:
-        want = run()
+        want = run(capi.GEMM_PERSISTENT)
     finally:
         capi.gemm_set_variant(0)
     assert torch.isfinite(want[0].float()).all()
     for _ in range(2):
-        got = run()
+        got = run(capi.GEMM_PINGPONG)
         assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
 
 

@@ -237,22 +237,27 @@ class Gemm:
         self.bias, self.pos = bias.to(F32).cuda(), pos.to(F32).cuda()
         self.what = f"gemm M={M} N={N} K={K} {ab_dtype} path {path} {kw}"
 
-    def _ran(self, tag):
+    def _ran(self, tag, c_dtype):
         got = self.capi.gemm_last_path()
         assert got == self.path, f"{self.what} {tag}: ran on path {got}"
+        # path 256 is two kernels: gemm256p.hip has the bf16 C except RESIDUAL_POS, gemm256.hip the rest
+        k = self.capi
+        tile = c_dtype == F32 or tag == "residual_pos"
+        want = {128: k.GEMM_GENERAL, 257: k.GEMM_PINGPONG, 256: k.GEMM_TILE if tile else k.GEMM_PERSISTENT}[self.path]
+        assert k.gemm_last_kernel() == want, f"{self.what} {tag}: ran on kernel {k.gemm_last_kernel()}, not {want}"
 
     def bias_store(self, c_dtype):
         """EPI_BIAS: C = acc + bias in f32, a bf16 C its one rounding."""
         c = nan_out(self.M, self.N, c_dtype)
         self.capi.gemm(self.a, self.w, c, self.bias, self.capi.EPI_BIAS, **self.kw)
-        self._ran("bias")
+        self._ran("bias", c_dtype)
         assert_exact(c, as_f32(self.acc + self.bias_i).to(c_dtype), f"{self.what} bias -> {c_dtype}")
 
     def bias_residual(self):
         """EPI_BIAS_RESIDUAL: x0 + acc + bias, in f32, in place."""
         c = self.res_i.to(F32).cuda()
         self.capi.gemm(self.a, self.w, c, self.bias, self.capi.EPI_BIAS_RESIDUAL, **self.kw)
-        self._ran("bias_residual")
+        self._ran("bias_residual", F32)
         assert_exact(c, as_f32(self.res_i + self.acc + self.bias_i), f"{self.what} bias_residual")
 
     def residual_pos(self, c_dtype, rows_per_frame, in_place):
@@ -263,7 +268,7 @@ class Gemm:
         c = res.clone() if in_place else nan_out(self.M, self.N, c_dtype)
         self.capi.gemm(self.a, self.w, c, None, self.capi.EPI_RESIDUAL_POS, pos=self.pos, tokens=rows_per_frame + 1, frames_per_clip=T_CLIP,
                        residual=None if in_place else res, **self.kw)
-        self._ran("residual_pos")
+        self._ran("residual_pos", c_dtype)
         assert_exact(c, want, f"{self.what} residual_pos -> {c_dtype} in_place={in_place}")
 
     def qkv_export(self, c_dtype, tokens, first):
@@ -281,7 +286,7 @@ class Gemm:
         ke, ve = nan_out(frames * (tokens - 1), D, c_dtype), nan_out(frames * (tokens - 1), D, c_dtype)
         self.capi.gemm(self.a, self.w[first * D:], c[:, first * D:], self.bias[first * D:], self.capi.EPI_QKV_EXPORT, pos=self.pos[:, :D].contiguous(),
                        k_export=ke, v_export=ve, tokens=tokens, frames_per_clip=T_CLIP, qkv_first=first, **self.kw)
-        self._ran(f"qkv_export first={first}")
+        self._ran(f"qkv_export first={first}", c_dtype)
         what = f"{self.what} qkv_export -> {c_dtype} qkv_first={first}"
         assert_exact(c[:, first * D:], as_f32(self.acc + self.bias_i)[:, first * D:].to(c_dtype), what + " C")
         assert first == 0 or bool(torch.isnan(c[:, :D]).all()), what + ": the query block was written"

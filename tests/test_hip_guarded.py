@@ -424,18 +424,22 @@ def test_gemm_tuned_paths(capi, M, N, K):
     prod = a.double() @ w.double().T
     ref = prod + bias.double()
     pingpong = K % 128 == 0 and K >= 384 and N % 256 == 0
-    paths = {}
+    paths, kernels = {}, {}
 
     def run(tag, epi, cdtype, want, atol, rtol, init=None, expect=None, use_bias=True, **kw):
         def op(b):
             c = b.out((M, N), cdtype, pad=8, init=init, name="C")
             capi.gemm(b.inp(a, pad=8, name="A"), b.inp(w, pad=64, name="W"), c, b.inp(bias, name="bias") if use_bias else None, epi, **kw)
             paths.setdefault(tag, []).append(capi.gemm_last_path())
+            kernels.setdefault(tag, []).append(capi.gemm_last_kernel())
             return {"C": c}
         d, gg = both(op)
         pd, pg = paths[tag]
         if expect is not None:
             assert (pd, pg) == (expect, expect), f"{tag}: paths {pd} (dense) / {pg} (guarded), expected {expect}"
+            # 256 is two kernels: the persistent one has the bf16 C, the one-workgroup-per-tile one the f32 C
+            kernel = capi.GEMM_PINGPONG if expect == 257 else capi.GEMM_TILE if cdtype == F32 else capi.GEMM_PERSISTENT
+            assert kernels[tag] == [kernel, kernel], f"{tag}: kernels {kernels[tag]}, expected {kernel}"
         verify(d, gg, {"C": (want, atol, rtol)}, same=_family(pd) == _family(pg), msg=f"tuned {tag} paths {pd}/{pg}")
 
     run("bias", capi.EPI_BIAS, BF16, ref, 1e-4, RT16, expect=257 if pingpong else 256)
@@ -526,10 +530,10 @@ def test_gemm_tuned_ldw_fallback(capi):
     def op(b):
         c = b.out((M, N), BF16, pad=8, name="C")
         capi.gemm(b.inp(a, pad=8), b.inp(w, pad=8), c, b.inp(bias), capi.EPI_BIAS_QUICKGELU)
-        paths.append(capi.gemm_last_path())
+        paths.append((capi.gemm_last_path(), capi.gemm_last_kernel()))
         return {"C": c}
     d, gg = both(op)
-    assert paths == [257, 256], paths
+    assert paths == [(257, capi.GEMM_PINGPONG), (256, capi.GEMM_PERSISTENT)], paths
     verify(d, gg, {"C": (_gelu_q(ref), 1e-4, RT16)}, msg="ldw = K + 8")
 
 

@@ -231,12 +231,16 @@ def test_gemm_tuned_kernel_every_epilogue(capi, M, N, K):
     capi.gemm(a, w, c, bias, capi.EPI_BIAS)
     # K a multiple of 128 and >= 384: the ping-pong kernel (257); other depths: the round-2 persistent kernel (256)
     assert capi.gemm_last_path() == (257 if K % 128 == 0 and K >= 384 and N % 256 == 0 else 256), "this shape must run on a tuned kernel"
+    assert capi.gemm_last_kernel() == (capi.GEMM_PINGPONG if K % 128 == 0 and K >= 384 else capi.GEMM_PERSISTENT)
+    # the plan hook answers for the call what the call then did (n_cu = 0: this device's)
+    assert capi.gemm_plan(capi.BF16, capi.BF16, capi.EPI_BIAS, M, N, K, n_cu=0).kernel == capi.gemm_last_kernel()
     assert_close(c, ref, 1e-4, RT, "bias")
     c.fill_(float("nan"))
     capi.gemm(a, w, c, bias, capi.EPI_BIAS_QUICKGELU)
     assert_close(c, ref * torch.sigmoid(1.702 * ref), 1e-4, RT, "quickgelu")
     cf = torch.full((M, N), float("nan"), device="cuda")
     capi.gemm(a, w, cf, bias, capi.EPI_BIAS)  # f32 store of the same product
+    assert capi.gemm_last_kernel() == capi.GEMM_TILE, "an f32 C is the one-workgroup-per-tile kernel's"
     assert_close(cf, ref, 1e-4, 1e-5, "bias, f32 out")
     x0 = torch.randn(M, N, device="cuda", generator=g)
     x = x0.clone()
@@ -302,6 +306,7 @@ def test_persistent_gemm_variants_are_bit_identical(capi, M, N, K, epi):
             ex["v_export"] = torch.full_like(ex["k_export"], float("nan"))
         capi.gemm(a, w, c, bias, e, **kw, **ex, **opts)
         assert capi.gemm_last_path() == expect_path[0]
+        assert capi.gemm_last_kernel() == (capi.GEMM_PINGPONG if expect_path[0] == 257 else capi.GEMM_PERSISTENT)
         return [c] + list(ex.values())
 
     base = run(tile_blocks=8)
@@ -345,7 +350,7 @@ def test_pingpong_gemm_ragged_panels_and_few_tiles(capi, M, N, K):
     try:
         want = torch.full((M, N), float("nan"), device="cuda", dtype=torch.bfloat16)
         capi.gemm(a, w, want, bias, capi.EPI_BIAS_QUICKGELU)
-        assert capi.gemm_last_path() == 256
+        assert capi.gemm_last_path() == 256 and capi.gemm_last_kernel() == capi.GEMM_PERSISTENT
     finally:
         capi.gemm_set_variant(0)
     assert_close(want, ref * torch.sigmoid(1.702 * ref), 1e-4, 2 ** -8, "round-2 kernel")
@@ -353,7 +358,7 @@ def test_pingpong_gemm_ragged_panels_and_few_tiles(capi, M, N, K):
         for opts in (dict(), dict(tile_blocks=8, stream_out=True), dict(tile_blocks=7)):
             c = torch.full((M, N), float("nan"), device="cuda", dtype=torch.bfloat16)
             capi.gemm(a, w, c, bias, capi.EPI_BIAS_QUICKGELU, **opts)
-            assert capi.gemm_last_path() == 257
+            assert capi.gemm_last_path() == 257 and capi.gemm_last_kernel() == capi.GEMM_PINGPONG
             assert torch.equal(c, want), (rep, opts)
 
 
@@ -438,7 +443,7 @@ def test_pingpong_residual_pos_equals_relaunching(capi, M, N, K, in_place, p):
     capi.gemm_set_variant(1)
     try:
         want = run()
-        assert capi.gemm_last_path() == 256
+        assert capi.gemm_last_path() == 256 and capi.gemm_last_kernel() == capi.GEMM_TILE
     finally:
         capi.gemm_set_variant(0)
     if p == 0:
@@ -450,7 +455,7 @@ def test_pingpong_residual_pos_equals_relaunching(capi, M, N, K, in_place, p):
         assert 0.4 < kept.float().mean().item() < 0.6, "about half of the elements keep their (doubled) product"
     for _ in range(2):
         got = run()
-        assert capi.gemm_last_path() == 257
+        assert capi.gemm_last_path() == 257 and capi.gemm_last_kernel() == capi.GEMM_PINGPONG
         assert torch.equal(got, want)
 
 
@@ -477,14 +482,14 @@ def test_persistent_gemm_raw_export_without_pos(capi, K):
         ke = torch.full((M // tokens * (tokens - 1), D), float("nan"), device="cuda", dtype=torch.bfloat16)
         ve = torch.full_like(ke, float("nan"))
         capi.gemm(a, w, c, bias, capi.EPI_QKV_EXPORT, pos=None, k_export=ke, v_export=ve, tokens=tokens, **opts)
-        assert capi.gemm_last_path() == path
+        assert capi.gemm_last_path() == path and capi.gemm_last_kernel() == (capi.GEMM_PINGPONG if path == 257 else capi.GEMM_PERSISTENT)
         assert_close(c, ref, 1e-4, 2 ** -8, f"qkv {opts}")  # (also: no NaN of the pre-fill left)
         assert_close(ke.view(-1, tokens - 1, D), fv[:, 1:, 1], 1e-4, 2 ** -8, f"k export {opts}")
         assert_close(ve.view(-1, tokens - 1, D), fv[:, 1:, 2], 1e-4, 2 ** -8, f"v export {opts}")
         # K and V blocks alone (qkv_first=1): identical exports and columns, the query block untouched
         c2, ke2, ve2 = torch.full_like(c, float("nan")), torch.full_like(ke, float("nan")), torch.full_like(ve, float("nan"))
         capi.gemm(a, w[D:], c2[:, D:], bias[D:], capi.EPI_QKV_EXPORT, pos=None, k_export=ke2, v_export=ve2, tokens=tokens, qkv_first=1, **opts)
-        assert capi.gemm_last_path() == path
+        assert capi.gemm_last_path() == path and capi.gemm_last_kernel() == (capi.GEMM_PINGPONG if path == 257 else capi.GEMM_PERSISTENT)
         assert torch.equal(ke2, ke) and torch.equal(ve2, ve) and torch.equal(c2[:, D:], c[:, D:]), opts
         assert torch.isnan(c2[:, :D].float()).all(), "the query block must not be written"
         return c, ke, ve
@@ -526,7 +531,7 @@ def test_patch_embed_tuned_kernel(capi, res, patch, width):
     wp[:, :kreal] = w.reshape(width, kreal)
     x = torch.full((n * tokens, width), float("nan"), device="cuda")
     capi.gemm(patches, wp.to(torch.bfloat16), x, None, capi.EPI_PATCH_EMBED, m=n * P, pos=pos, cls=cls, tokens=tokens)
-    assert capi.gemm_last_path() == 256
+    assert capi.gemm_last_path() == 256 and capi.gemm_last_kernel() == capi.GEMM_TILE
     assert_close(x.view(n, tokens, width), want, 2e-4, 1e-5, "patch embed")
 
 

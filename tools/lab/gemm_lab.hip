@@ -5,7 +5,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <vector>
-#include "../../dfd-clip_amd/csrc/gemm_args.hpp"
+#include "../../dfd-clip_amd/csrc/gemm_plan.hpp"
 
 int dfd_gemm256q_launch(const GemmArgs& a, int epi, hipStream_t st);  // gemm256q_lab.hip
 int dfd_gemm256e_launch(const GemmArgs& a, int epi, int depth, hipStream_t st);  // gemm256e_lab.hip (ping-pong K loop)
@@ -39,7 +39,16 @@ int main(int argc, char** argv) {
       a.tile_rows = v.rows; a.stream_out = v.stream;
       if (v.persistent == 2) return dfd_gemm256q_launch(a, sh.epi, 0);
       if (v.persistent == 3) return dfd_gemm256e_launch(a, sh.epi, v.depth, 0);
-      return v.persistent ? dfd_gemm256p_try(a, DFD_BF16, sh.epi, 0) : dfd_gemm256_try(a, DFD_BF16, sh.epi, 0);
+      // the product's plan with the ping-pong kernel skipped (P); for the relaunching kernel, which the product never gives a
+      // bf16 C the persistent kernel serves, the same plan re-shaped to one workgroup per 256-row tile
+      GemmPlan p = gemm_plan(a, gemm_ptrs(a), DFD_BF16, DFD_BF16, sh.epi, 1, 0, dfd_cu_count());
+      if (v.persistent) return dfd_gemm256p_launch(p, a, false, false, 0);
+      p.kernel = DFD_GEMM_TILE;
+      p.tiles.rows = 256;
+      p.tiles.tiles_m = (int)((M + 255) / 256);
+      p.tiles.ntiles = (int64_t)p.tiles.tiles_m * (sh.N / 256);
+      p.tiles.grid = (int)p.tiles.ntiles;
+      return dfd_gemm256_launch(p, a, DFD_BF16, 0);
     };
     for (int i = 0; i < 20; ++i) run(vars[0]);
     hipDeviceSynchronize();

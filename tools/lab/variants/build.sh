@@ -6,7 +6,7 @@ python3 gen.py
 F="--offload-arch=gfx950 -O3 -std=c++17 -I../../../include"
 mkdir -p ../build
 for v in 1 2 3; do
-  hipcc $F -Ddfd_gemm256p_try=dfd_gemm256p_try_v$v -Ddfd_gemm256p_f8_try=dfd_gemm256p_f8_try_v$v -c v$v.hip -o ../build/v$v.o &
+  hipcc $F -Ddfd_gemm256p_launch=dfd_gemm256p_launch_v$v -c v$v.hip -o ../build/v$v.o &
 done
 hipcc $F -c ../../../dfd-clip_amd/csrc/gemm256p.hip -o ../build/k256p.o &
 wait
