@@ -9,9 +9,11 @@ launch (`csrc/align.hip`, `include/dfdclip_align.h`) that computes only the cut,
   FaceAligner(reference, canvas=256, crop=150, stable_points=..., start_idx=15, stop_idx=68, smooth=0, border=0)
       .plan(landmarks [F,68,2], transforms=None) -> AlignPlan    plain host data
       .apply(frames_u8, plan, layout="hwc", swap_rb=False)       -> [F,3,crop,crop] uint8 on the frames' device
+      .apply_yuv(src, plan, matrix=None)                         the same from a 4:2:0 source (`yuv.Yuv420`: NV12, I420, ...)
   AlignPlan   .forward / .inverse [F,2,3], .origin [F,2] (x0, y0), .valid [F], .records (dfd_align_frame_t as a NumPy record)
       .window(margin, frame_size) -> ((win_h, win_w), origins [F,2])   one window size and per-frame origins that cover every
                                                                      tap of every valid frame: upload only the face region
+                                                                     (`even=True`: even origins, for 4:2:0 sources)
       .with_window(origins, (win_h, win_w)) -> AlignPlan             the plan for frames sliced that way
   align_reference(frames, plan, ...)   NumPy int64 restatement of the kernel; the GPU tests demand equality bit for bit
 
@@ -152,17 +154,22 @@ class AlignPlan:
         out[~self.valid] = 0
         return out
 
-    def window(self, margin=0, frame_size=None):
+    def window(self, margin=0, frame_size=None, even=False):
         """((win_h, win_w), origins [F,2] int64 as (x, y)): one window size and a per-frame origin in full-frame coordinates
         such that every tap of every valid frame lies inside its window (plus `margin` pixels on every side).  With
         `frame_size=(H, W)` the windows are kept inside the frame, which loses nothing: a tap outside the frame is `border`
         either way.  The caller slices `frame[y:y+win_h, x:x+win_w]` on the host, uploads the slices and applies
-        `with_window(origins, (win_h, win_w))`."""
+        `with_window(origins, (win_h, win_w))`.
+        `even=True` (4:2:0 sources, `apply_yuv`): every origin is even, so that the chroma of a window is the chroma of its
+        frame, and every tap is still covered; the sizes are even too, except along an odd `frame_size` dimension, where they
+        are odd (no even-sized window at an even origin reaches an odd frame's last column)."""
         margin = int(margin)
         fp = self.footprint()
         v = self.valid
         if not v.any():
-            return (1, 1), np.zeros((len(v), 2), dtype=np.int64)
+            return ((2, 2) if even else (1, 1)), np.zeros((len(v), 2), dtype=np.int64)
+        if even:
+            return self._even_window(fp, margin, frame_size)
         win_w = int((fp[v, 2] - fp[v, 0]).max()) + 1 + 2 * margin
         win_h = int((fp[v, 3] - fp[v, 1]).max()) + 1 + 2 * margin
         origins = np.where(v[:, None], fp[:, :2] - margin, 0)
@@ -171,6 +178,25 @@ class AlignPlan:
             win_h, win_w = min(win_h, H), min(win_w, W)
             origins = np.stack([np.clip(origins[:, 0], 0, W - win_w), np.clip(origins[:, 1], 0, H - win_h)], axis=1)
         return (win_h, win_w), origins.astype(np.int64)
+
+    def _even_window(self, fp, margin, frame_size):
+        v = self.valid
+        sizes, origins = [], []
+        for axis in (0, 1):                                   # x, then y
+            lo, hi = fp[:, axis] - margin, fp[:, axis + 2] + margin
+            n = None if frame_size is None else int(frame_size[1 - axis])
+            if n is not None:                                 # what lies outside the frame is border with or without a window
+                lo, hi = np.clip(lo, 0, n - 1), np.clip(hi, 0, n - 1)
+            lo = np.where(v, lo - (lo & 1), 0)                # down to the even neighbour (also for negative origins)
+            size = int((hi - lo)[v].max()) + 1
+            parity = 0 if n is None else n & 1                # n - size even: the last origin that fits is even as well
+            size += (size & 1) ^ parity
+            if n is not None:
+                size = min(size, n)
+                lo = np.minimum(lo, n - size)
+            sizes.append(size)
+            origins.append(lo)
+        return (sizes[1], sizes[0]), np.stack(origins, axis=1).astype(np.int64)
 
     def with_window(self, origins, size):
         """The same plan for frames of which only the window `size` = (win_h, win_w) at `origins` [F,2] (x, y) is held."""
@@ -267,6 +293,27 @@ class FaceAligner:
             ok, rs, fs = strides(x)
         out = torch.empty(F, 3, plan.crop, plan.crop, dtype=torch.uint8, device=x.device)
         return capi.align_crop_u8(x, out, plan.on(x.device), _LAYOUTS[layout], rs, fs, H, W, swap_rb=swap_rb)
+
+    @staticmethod
+    def apply_yuv(src, plan, matrix=None):
+        """A `yuv.Yuv420` (NV12 / NV21 / I420 / YV12 device planes, read where they lie) -> a new tensor [F,3,crop,crop]; one
+        launch that converts tap by tap under `matrix` (`yuv.matrix(...)`, default BT.601 limited range): the bits of
+        `apply(yuv.to_rgb(src, matrix), plan, layout="chw")` without the converted frames.  A plan made by `with_window` takes
+        the windows; their origins must be even (`plan.window(..., even=True)`), or the window's chroma samples would not be
+        the frame's."""
+        import torch
+        from . import yuv
+        if not isinstance(src, yuv.Yuv420):
+            raise TypeError(f"FaceAligner.apply_yuv takes a yuv.Yuv420 (device planes as the decoder delivered them), got {type(src).__name__}")
+        if len(src) != len(plan):
+            raise ValueError(f"the plan holds {len(plan)} frames, the source {len(src)}")
+        if plan.win_size is not None and plan.win_size != (src.height, src.width):
+            raise ValueError(f"the plan was made for {plan.win_size[0]}x{plan.win_size[1]} windows, the frames are {src.height}x{src.width}")
+        if (plan.win_origin[plan.valid] & 1).any():
+            raise ValueError("apply_yuv: a window starts on an odd full-frame coordinate, so its chroma samples are not the frame's; "
+                             "make the windows with plan.window(..., even=True)")
+        out = torch.empty(len(src), 3, plan.crop, plan.crop, dtype=torch.uint8, device=src.device)
+        return capi.align_crop_yuv420(src.source(), src.height, src.width, out, plan.on(src.device), yuv._c_matrix(matrix))
 
     def __call__(self, frames_u8, landmarks, layout="hwc", swap_rb=False):
         plan = self.plan(landmarks)

@@ -25,9 +25,10 @@ FLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-
 # there, and it is not in the list.  Both kernels inline one epilogue, tile_epilogue in gemm256p_common.hpp.)
 # align.hip has no hand-counted waits; it is listed because a spill in its tap loop would put scratch traffic on a kernel
 # whose whole cost is memory operations.  elastic.hip's remap kernel is listed for the same reason: it holds sixteen tap
-# offsets and weights per lane across its frame loop (both instantiations are checked).
+# offsets and weights per lane across its frame loop (both instantiations are checked).  yuv.hip's two kernels (both names
+# hold "yuv420_") are byte movers as well: the converter keeps six 8-byte results per lane, the fused gather align.hip's state.
 NO_SCRATCH = {"gemm256e.hip": "gemm256e_kernel", "attention_mfma_xrow.hip": "attn_mfma_xrow_kernel", "align.hip": "align_crop_u8_kernel",
-              "elastic.hip": "elastic_remap_u8_kernel"}
+              "elastic.hip": "elastic_remap_u8_kernel", "yuv.hip": "yuv420_"}
 
 
 def _hipcc():
@@ -77,6 +78,7 @@ def build(force=False, verbose=False, extra_flags=()):
     headers.append(os.path.join(INCLUDE, "dfdclip_augment.h"))
     headers.append(os.path.join(INCLUDE, "dfdclip_align.h"))
     headers.append(os.path.join(INCLUDE, "dfdclip_elastic.h"))
+    headers.append(os.path.join(INCLUDE, "dfdclip_yuv.h"))
     headers.append(os.path.join(INCLUDE, "dfdclip_hooks.h"))
     jobs, objs = [], []
     for src in sources():

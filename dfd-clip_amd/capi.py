@@ -187,6 +187,30 @@ ALIGN_SIGNATURES = {
                                   c_void_p]),
 }
 
+
+class YuvMatrix(Structure):
+    """dfd_yuv_matrix_t (include/dfdclip_yuv.h): the Q16 conversion matrix of one call; host data."""
+    _fields_ = [("y_off", c_int32), ("cy", c_int32), ("crv", c_int32), ("cgu", c_int32), ("cgv", c_int32), ("cbu", c_int32),
+                ("reserved", c_int32 * 2)]
+
+
+class Yuv420Source(Structure):
+    """dfd_yuv420_t (include/dfdclip_yuv.h): three device planes and their byte strides; host data."""
+    _fields_ = [("y", c_void_p), ("u", c_void_p), ("v", c_void_p), ("y_row_stride", c_int64), ("y_frame_stride", c_int64),
+                ("c_row_stride", c_int64), ("c_frame_stride", c_int64), ("c_px_stride", c_int32), ("reserved", c_int32)]
+
+
+YUV_MATRIX_BYTES = ctypes.sizeof(YuvMatrix)    # the header documents it as DFD_YUV_MATRIX_BYTES
+YUV420_BYTES = ctypes.sizeof(Yuv420Source)     # ... as DFD_YUV420_BYTES
+YUV_COEF_MAX = 1 << 21
+
+# 4:2:0 sources beside the ABI, in a header of its own (include/dfdclip_yuv.h)
+YUV_SIGNATURES = {
+    "dfd_yuv420_to_rgb_u8": (c_int, [POINTER(Yuv420Source), c_int, c_int, c_void_p, c_int, POINTER(YuvMatrix), c_void_p]),
+    "dfd_align_crop_yuv420": (c_int, [POINTER(Yuv420Source), c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, POINTER(YuvMatrix),
+                                      c_void_p]),
+}
+
 ELASTIC_MAX_RADIUS, ELASTIC_TAP_ONE, ELASTIC_SITE = 128, 32768, 0xE1A57100
 
 # elastic warp (the reference's `ssl_fake`) beside the ABI, in a header of its own (include/dfdclip_elastic.h)
@@ -252,7 +276,7 @@ def load_library(path=None):
         raise DfdError(f"{path} not found: the HIP kernel library is not built and there is no fallback path")
     lib = ctypes.CDLL(path)
     for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **EXPLAIN_SIGNATURES, **AUGMENT_SIGNATURES, **ALIGN_SIGNATURES,
-                               **ELASTIC_SIGNATURES, **HOOK_SIGNATURES}.items():
+                               **ELASTIC_SIGNATURES, **YUV_SIGNATURES, **HOOK_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError:
@@ -432,6 +456,30 @@ def align_crop_u8(src, out, records, layout, row_stride, frame_stride, win_h, wi
         assert span <= have, f"the strides describe {span} bytes, the tensor's memory holds {have} from its first element on"
     _check(load_library().dfd_align_crop_u8(_ptr(src), int(layout), int(row_stride), int(frame_stride), int(win_h), int(win_w), _ptr(out),
                                             n, oh, ow, _ptr(records), ALIGN_SWAP_RB if swap_rb else 0, _stream()), "dfd_align_crop_u8")
+    return out
+
+
+def yuv420_to_rgb_u8(source, out, matrix):
+    """out [n,3,h,w] u8 = the n frames of `source` (a Yuv420Source whose planes are device memory) as RGB under `matrix` (a
+    YuvMatrix); include/dfdclip_yuv.h.  The caller answers for the memory behind the three pointers (yuv.Yuv420 derives them
+    from tensor views, which cannot describe more than they hold)."""
+    _dev(out)
+    assert out.dtype == torch.uint8 and out.dim() == 4 and out.shape[1] == 3 and out.is_contiguous()
+    n, _, h, w = out.shape
+    _check(load_library().dfd_yuv420_to_rgb_u8(ctypes.byref(source), h, w, _ptr(out), n, ctypes.byref(matrix), _stream()),
+           "dfd_yuv420_to_rgb_u8")
+    return out
+
+
+def align_crop_yuv420(source, win_h, win_w, out, records, matrix):
+    """out [n,3,oh,ow] u8 = the face-aligned crops of the n 4:2:0 windows of `source` (win_h x win_w pixels each), converted
+    under `matrix` tap by tap; `records` u8 [n, ALIGN_FRAME_BYTES] = dfd_align_frame_t on the device (include/dfdclip_yuv.h)."""
+    _dev(out, records)
+    assert out.dtype == torch.uint8 and out.dim() == 4 and out.shape[1] == 3 and out.is_contiguous()
+    n, _, oh, ow = out.shape
+    assert records.dtype == torch.uint8 and records.is_contiguous() and tuple(records.shape) == (n, ALIGN_FRAME_BYTES)
+    _check(load_library().dfd_align_crop_yuv420(ctypes.byref(source), int(win_h), int(win_w), _ptr(out), n, oh, ow, _ptr(records),
+                                                ctypes.byref(matrix), _stream()), "dfd_align_crop_yuv420")
     return out
 
 

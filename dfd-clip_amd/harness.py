@@ -25,8 +25,8 @@ code, so that a reference user finds the same step semantics on top of `Detector
   infer_videos    `inference.py:105-162`: per video, chunks of `batch_size` clips -> predict -> softmax ->
                   clip- or video-level (mean over clips) probabilities -> gather -> accuracy / AUROC with
                   the dummy [0, 1] pair the reference appends before computing.
-  infer_raw_video `pipeline.py:114-182` + `:328-351`: decoded frames + landmarks -> face-aligned crops on the device
-                  (`align.FaceAligner`) -> clips of num_frames, ragged tail dropped -> predict in chunks -> softmax ->
+  infer_raw_video `pipeline.py:114-182` + `:328-351`: decoded frames (RGB tensors, or the decoder's 4:2:0 surfaces as a
+                  `yuv.Yuv420`) + landmarks -> face-aligned crops on the device (`align.FaceAligner`) -> clips of num_frames, ragged tail dropped -> predict in chunks -> softmax ->
                   mean over clips -> probability of class 1.
 """
 import copy
@@ -268,19 +268,30 @@ def infer_videos(model, videos, batch_size=30, modality="video", task_index=0, d
 
 
 @torch.no_grad()
-def infer_raw_video(model, frames, landmarks, aligner, batch_size=16, task_index=0, layout="hwc", swap_rb=False, with_logits=False):
+def infer_raw_video(model, frames, landmarks, aligner, batch_size=16, task_index=0, layout="hwc", swap_rb=False, with_logits=False,
+                    matrix=None):
     """One decoded video to a verdict, as `pipeline.get_result` does after its file handling (`pipeline.py:328-351`), with
     the face alignment it reads from a pre-cropped file done here on the device (`align.FaceAligner`).
 
     frames: uint8 device frames [F,H,W,3] (`layout="hwc"`) or [F,3,H,W]; landmarks [F,68,2]; `aligner.plan` /
-    `aligner.apply` turn them into [F,3,crop,crop] crops.  The frames are cut into clips of `model.num_frames`
+    `aligner.apply` turn them into [F,3,crop,crop] crops.  A `yuv.Yuv420` (the decoder's NV12 / I420 surfaces on the device)
+    goes through `aligner.apply_yuv` with `matrix` (`yuv.matrix(...)`, default BT.601 limited range) instead; `layout` and
+    `swap_rb` do not apply to it (NV21 is `Yuv420.nv12(..., swap_uv=True)`).  The frames are cut into clips of `model.num_frames`
     consecutive frames, a ragged last clip is dropped (`pipeline.py:334-336`), `predict` runs on uint8 clips in chunks of
     `batch_size` with `plan.valid` (frames with a face) as the mask, and the softmax is averaged over clips.
     Returns (probability of class 1, per-clip probabilities [clips, classes]) on the host; `with_logits` appends the
     per-clip logits."""
     model.eval()
     plan = aligner.plan(landmarks)
-    crops = aligner.apply(frames, plan, layout=layout, swap_rb=swap_rb)
+    from .yuv import Yuv420
+    if isinstance(frames, Yuv420):
+        if swap_rb:
+            raise ValueError("swap_rb is for interleaved BGR tensors; a Yuv420 source names its own u and v planes")
+        crops = aligner.apply_yuv(frames, plan, matrix=matrix)
+    else:
+        if matrix is not None:
+            raise ValueError("matrix= converts a yuv.Yuv420 source; RGB tensors take none")
+        crops = aligner.apply(frames, plan, layout=layout, swap_rb=swap_rb)
     T = int(model.num_frames)
     n = crops.shape[0] // T
     if n == 0:

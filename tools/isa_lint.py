@@ -1,11 +1,18 @@
 #!/usr/bin/env python3
-"""ISA lint for the gfx950 kernels: no vector store of more than 8 bytes per lane with a REGISTER in its scalar-offset field.
+"""ISA lint for the gfx950 kernels, two rules.
+
+1. No vector store of more than 8 bytes per lane with a REGISTER in its scalar-offset field.
 
 Why: between such a store and a VALU write of its data registers the hardware needs wait states; the compiler inserts them
 — except when the scalar-offset field holds a register (LLVM's GCNHazardRecognizer::createsVALUHazard exempts that form).
 On gfx950 the exempted form was seen to go out with the following instruction's result in its first data register
 (attention_mfma_xrow.hip, round 3; csrc/attention_common.hpp: attn_store_line).  Keeping the field at 0 makes the compiler's
 own hazard handling apply.
+
+2. No v_ashr_pk_u8_i32 / v_ashr_pk_i8_i32.  hipcc selects them for `clamp(a >> n) | clamp(b >> n) << 8` and goes on to OR
+further bytes into the upper half of the result as if that half were zero; on gfx950 the upper 16 bits of the destination
+were seen to keep what the register held before (csrc/yuv.hip's converter, whose packed dwords came out with bytes 2 and 3
+OR-ed with stale bits; `packable` there keeps the pattern from forming).
 
 usage: isa_lint.py [file.hip ...]   (default: every csrc/*.hip); exit code 1 and one line per finding.
 Compiles the device code of each file to assembly with hipcc (no GPU needed)."""
@@ -18,6 +25,7 @@ from concurrent.futures import ThreadPoolExecutor
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "dfd-clip_amd", "csrc")
 STORE = re.compile(r"^\s*(buffer_store_dwordx[34]|buffer_store_b(96|128))\s+(.*)$")
+PACKED_SHIFT = re.compile(r"^\s*(v_ashr_pk_[ui]8_i32)\b")
 
 
 def device_asm(path):
@@ -32,6 +40,10 @@ def findings(asm, name):
         m = re.match(r"^([A-Za-z_][\w$.]*):", line)
         if m and not line.startswith(".L"):
             kernel = m.group(1)
+        m = PACKED_SHIFT.match(line)
+        if m:
+            out.append(f"{name}: {kernel}: asm line {n}: `{line.strip()}`: {m.group(1)} leaves the upper half of its destination as it was")
+            continue
         m = STORE.match(line)
         if not m:
             continue
