@@ -219,6 +219,14 @@ ELASTIC_SIGNATURES = {
     "dfd_elastic_remap_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
 }
 
+SWIGLU_VEC16, SWIGLU_ELEMENT = 1, 2  # dfd_swiglu_last_path: 16-byte accesses, or element by element
+
+# the gate of a SwiGLU feed-forward (DINOv2 ViT-g/14) beside the ABI, in a header of its own (include/dfdclip_swiglu.h)
+SWIGLU_SIGNATURES = {
+    "dfd_swiglu_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int64, c_int, c_void_p]),
+    "dfd_swiglu_last_path": (c_int, []),
+}
+
 # test / measurement hooks outside the ABI header (include/dfdclip_hooks.h)
 class AttentionPlan(Structure):
     """dfd_attention_plan_t (include/dfdclip_hooks.h)."""
@@ -276,7 +284,7 @@ def load_library(path=None):
         raise DfdError(f"{path} not found: the HIP kernel library is not built and there is no fallback path")
     lib = ctypes.CDLL(path)
     for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **EXPLAIN_SIGNATURES, **AUGMENT_SIGNATURES, **ALIGN_SIGNATURES,
-                               **ELASTIC_SIGNATURES, **YUV_SIGNATURES, **HOOK_SIGNATURES}.items():
+                               **ELASTIC_SIGNATURES, **YUV_SIGNATURES, **SWIGLU_SIGNATURES, **HOOK_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError:
@@ -515,6 +523,26 @@ def elastic_remap_u8(clips, out, field, field_of_clip):
 
 
 _profile = {"epilogue": None, "events": [], "base": None}
+
+
+def swiglu_fwd(x12, hidden):
+    """hidden[r, j] = silu(x12[r, j]) * x12[r, H + j] (include/dfdclip_swiglu.h): x12 [rows, 2H], hidden [rows, H], both bf16 or both
+    f32, unit column stride, any row stride (views of wider buffers are fine); x12 is read once, nothing between the rows of
+    `hidden` is written."""
+    _dev(x12, hidden)
+    assert x12.dim() == 2 and hidden.dim() == 2 and x12.shape == (hidden.shape[0], 2 * hidden.shape[1]), (x12.shape, hidden.shape)
+    assert x12.dtype == hidden.dtype and x12.dtype in _DTYPE, (x12.dtype, hidden.dtype)
+    assert x12.stride(1) == 1 and hidden.stride(1) == 1
+    rows, H = hidden.shape
+    _check(load_library().dfd_swiglu_fwd(_ptr(x12), x12.stride(0) if rows > 1 else max(x12.stride(0), 2 * H), _ptr(hidden),
+                                         hidden.stride(0) if rows > 1 else max(hidden.stride(0), H), _DTYPE[x12.dtype], rows, H, _stream()),
+           "dfd_swiglu_fwd")
+    return hidden
+
+
+def swiglu_last_path():
+    """SWIGLU_VEC16 / SWIGLU_ELEMENT: the form the last `swiglu_fwd` of this thread launched (0: none, or a no-op)."""
+    return load_library().dfd_swiglu_last_path()
 
 
 def profile_gemm(epilogue=None):

@@ -121,10 +121,12 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 512 ? (POS ? 2 : 3) : 4)) void decod
 __global__ void decoder_attn_combine_kernel(const float* __restrict__ ws, float* __restrict__ mix,
                                             float* __restrict__ mix_softmax, float* __restrict__ stats, int splits,
                                             int heads) {
-  extern __shared__ float cw[];  // [heads][splits] rescale weights exp(m_split − M)
+  extern __shared__ float cw[];  // [heads of this block][splits] rescale weights exp(m_split − M)
   __shared__ float sM[16], sL[16];
   const int b = blockIdx.x;
-  const int hd = threadIdx.x / HD, c = threadIdx.x % HD;
+  // a block merges blockDim.x / 64 heads, at most 16: all of them (grid.y = 1) up to 16 heads, the group blockIdx.y beyond
+  const int hl = threadIdx.x / HD, c = threadIdx.x % HD;
+  const int hd = blockIdx.y * (blockDim.x / HD) + hl;
   const float* base = ws + (int64_t)b * splits * heads * PART;
   // stage 1: one wave-parallel pass over the (split, head) states instead of a serial chain per thread
   if (c < 64) {
@@ -135,28 +137,28 @@ __global__ void decoder_attn_combine_kernel(const float* __restrict__ ws, float*
     for (int s = c; s < splits; s += 64) {
       const float* o = base + ((int64_t)s * heads + hd) * PART;
       const float w = (o[0] == -INFINITY) ? 0.f : __expf(o[0] - M);
-      cw[hd * splits + s] = w;
+      cw[hl * splits + s] = w;
       L = fmaf(o[1], w, L);
     }
     L = wave_sum(L);
-    if (c == 0) { sM[hd] = M; sL[hd] = L; }
+    if (c == 0) { sM[hl] = M; sL[hl] = L; }
   }
   __syncthreads();
-  const float L = sL[hd];
+  const float L = sL[hl];
   float As = 0.f, Ac = 0.f;
   const float* col = base + (int64_t)hd * PART + 2 + c;
 #pragma unroll 8
   for (int s = 0; s < splits; ++s) {
     const float* o = col + (int64_t)s * heads * PART;
-    As = fmaf(o[0], cw[hd * splits + s], As);
+    As = fmaf(o[0], cw[hl * splits + s], As);
     Ac += o[HD];
   }
   // (softmax branch + CoDA branch) / n_act, n_act = 2 (models.py:140-142).  All keys masked:
   // L == 0 -> NaN, as the reference's softmax over all -inf.
-  mix[(int64_t)b * heads * HD + threadIdx.x] = 0.5f * (As / L) + 0.5f * Ac;
-  if (mix_softmax != nullptr) mix_softmax[(int64_t)b * heads * HD + threadIdx.x] = As / L;
+  mix[((int64_t)b * heads + hd) * HD + c] = 0.5f * (As / L) + 0.5f * Ac;
+  if (mix_softmax != nullptr) mix_softmax[((int64_t)b * heads + hd) * HD + c] = As / L;
   if (c == 0) {
-    stats[((int64_t)b * heads + hd) * 2 + 0] = sM[hd];
+    stats[((int64_t)b * heads + hd) * 2 + 0] = sM[hl];
     stats[((int64_t)b * heads + hd) * 2 + 1] = L;
   }
 }
@@ -464,8 +466,12 @@ extern "C" int dfd_decoder_attn_fwd(const float* q, const void* k, const void* v
                              patches, heads, blk.R, lay, divp);
       });
   if (rc != DFD_OK) return rc;
+  // one thread per channel of up to 16 heads; wider towers (ViT-g/14: 24 heads) merge their heads in equal groups on grid.y
+  int hpb = heads < 16 ? heads : 16;
+  while (heads % hpb != 0) --hpb;
   return launch_kernel("dfd_decoder_attn_fwd(combine)", decoder_attn_combine_kernel,
-                       Launch{dim3(B), dim3(heads * HD), combine_lds, st, combine_static}, ws, mix, mix_softmax, stats, splits, heads);
+                       Launch{dim3(B, heads / hpb), dim3(hpb * HD), (size_t)hpb * splits * sizeof(float), st, combine_static}, ws, mix,
+                       mix_softmax, stats, splits, heads);
 }
 
 // shared by the attn_mode entry points (declared in decoder_common.hpp for decoder_bwd.hip)

@@ -231,7 +231,7 @@ inline int check_decoder_attn(const char* who, bool given, std::initializer_list
                               const dfd_kv_layout_t* l, int B, int T, int patches, int heads, int d) {
   DFD_REQUIRE(given, "%s: null pointer", who);
   DFD_REQUIRE(d == HD, "%s: head dim %d, only 64 is supported", who, d);
-  DFD_REQUIRE(B >= 0 && T > 0 && patches > 0 && heads > 0 && heads * HD <= 1024, "%s: bad shape", who);
+  DFD_REQUIRE(B >= 0 && T > 0 && patches > 0 && heads > 0 && heads * HD <= 4096, "%s: bad shape", who);  // (4096: dfd_layernorm's widest row)
   DFD_REQUIRE(decoder_attn_block(heads).threads <= 1024, "%s: heads=%d needs %d threads", who, heads, decoder_attn_block(heads).threads);
   DFD_REQUIRE(kv_dtype == DFD_F32 || kv_dtype == DFD_BF16, "%s: kv_dtype=%d", who, kv_dtype);
   for (const void* p : aligned16) DFD_REQUIRE(dfd_aligned16(p), "%s: pointers must be 16-byte aligned", who);

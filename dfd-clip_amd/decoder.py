@@ -115,6 +115,10 @@ class Decoder(RuntimeStateMixin, nn.Module):
             if hasattr(src, "norm1"):  # a DINOv2 block: norm1 / norm2, mlp.fc1 / fc2 (models.py:192-209)
                 dst.ln_1.load_state_dict(src.norm1.state_dict())
                 dst.ln_2.load_state_dict(src.norm2.state_dict())
+                if hasattr(src.mlp, "w12"):
+                    # a SwiGLU block (ViT-g/14) has no fc1 / fc2: the reference's name map covers those two only, and a
+                    # decoder block is c_fc -> QuickGELU -> c_proj whatever the tower runs.  Its mlp keeps its own start.
+                    continue
                 names = {"fc1": "c_fc", "fc2": "c_proj"}
                 dst.mlp.load_state_dict({names[k.split(".")[0]] + "." + k.split(".", 1)[1]: v for k, v in src.mlp.state_dict().items()})
                 continue

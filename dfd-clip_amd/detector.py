@@ -11,8 +11,10 @@ libdfdclip_hip.so; PyTorch supplies device memory, streams and the tiny per-samp
 `precision` is the only addition to the reference signature: "fp32" is the parity path
 (logits within 1e-3 of the reference's fp32 CPU result), "bf16" the throughput path, "fp8" the bf16 path
 with the encoder's large projections on e4m3 matrix-core operands (BASELINE configs[4]; `calibrate_fp8`).
-`config.foundation` selects the frozen tower: "clip" (`architecture` names it) or "dinov2" (ViT-B/14, dinov2.py;
-fp32 and bf16; a CLIP model name in `architecture` is ignored as in the reference, see `weights.model_arch`).
+`config.foundation` selects the frozen tower: "clip" (`architecture` names it) or "dinov2" (ViT-B/14, dinov2.py, or the
+tower `architecture` names: dinov2_vits14 / dinov2_vitb14 / dinov2-large (ViT-L/14) / dinov2_vitg14, `weights.DINO_ALIASES`; fp32 and bf16, fp8 where the width is
+a multiple of 256 and the feed-forward an MLP; a CLIP model name in `architecture` is ignored as in the reference, see
+`weights.model_arch`).
 """
 import contextlib
 import logging

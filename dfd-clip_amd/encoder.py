@@ -27,6 +27,10 @@ HBM layout for a batch of N frames (M = N*tokens rows, D = width), all row-major
   qkv  [M, 3D]  act   q | k | v column blocks, head = 64 contiguous columns
   mix  [M, D]   act   attention output
   u    [M, 4D]  act   QuickGELU(c_fc) output
+A tower with a SwiGLU feed-forward (`ffn_hidden` = H > 0: DINOv2 ViT-g/14, dinov2.py) has, instead of `u`,
+  x12     [M, 2H]  act   the w12 projection, gate half | value half
+  hidden  [M, Hp]  act   silu(x12[:, :H]) * x12[:, H:] (dfd_swiglu_fwd), Hp = H rounded up to the GEMM's K step of 32; the pad
+                         columns are zero and meet zero columns of w3
 `extract_kv` additionally writes the decoder's K/V operands straight from the QKV GEMM
 epilogue: `[N*P, D]` per selected layer, CLS row dropped, temporal positional embedding added
 (reference `src/models.py:505-509`, `:326-334`), and skips the work of the last selected
@@ -172,6 +176,9 @@ class VisionTransformer(RuntimeStateMixin, nn.Module):
     # the parameters (`__init__`, `_param_device`) and how they are staged for the kernels (`_stage`).
     ln_eps = 1e-5
     act_epilogue = capi.EPI_BIAS_QUICKGELU
+    # hidden channels H of a SwiGLU feed-forward (w12 -> silu(x1) * x2 -> w3), 0: the MLP (c_fc -> activation -> c_proj, 4D
+    # channels).  Such a tower stages w_12 / b_12 / w_3 / b_3 per block instead of w_fc / b_fc / w_proj / b_proj.
+    ffn_hidden = 0
 
     def __init__(self, input_resolution, patch_size, width, layers, heads, output_dim, precision="bf16"):
         super().__init__()
@@ -376,6 +383,8 @@ class VisionTransformer(RuntimeStateMixin, nn.Module):
         if self.act_dtype != torch.bfloat16:
             return
         for bp in p["blocks"]:
+            if "w_fc" not in bp:  # a SwiGLU layer: its intermediate goes through the gate kernel, row-major
+                continue
             H = bp["w_fc"].shape[0]
             if H % 64 == 0 and bp["w_proj"].shape[1] == H:
                 idx = blocked.fc_channel_perm(H, device=bp["w_fc"].device)
@@ -416,14 +425,17 @@ class VisionTransformer(RuntimeStateMixin, nn.Module):
         return p
 
     def _ws_key(self, n, keep_layers, slot):
-        return (n, self.precision, keep_layers, slot, self._fp8_needs(n * self.tokens))
+        return (n, self.precision, keep_layers, slot, self.ffn_hidden, self._fp8_needs(n * self.tokens))
 
     def _workspace(self, n, keep_layers, slot=0):
         """Activation buffers for n frames.  Rows are padded to a multiple of 256 so tiled kernels
         never read out of bounds; pad rows hold zeros/garbage that is never stored to real rows.
-        The e4m3 `h8` / `u8` and the bf16 `u` exist only where the fp8 policy has a projection that touches them."""
+        The e4m3 `h8` / `u8` and the bf16 `u` exist only where the fp8 policy has a projection that touches them; a SwiGLU
+        tower has `x12` and `hidden` in place of `u`."""
         key = self._ws_key(n, keep_layers, slot)
         need_h8, need_u8, need_u = key[-1]
+        H = self.ffn_hidden
+        need_u = need_u and H == 0
         ws = self._ws.get(key)
         if ws is None:
             dev = self._param_device()
@@ -440,6 +452,9 @@ class VisionTransformer(RuntimeStateMixin, nn.Module):
                 delta=torch.zeros(Mp, D, device=dev, dtype=act) if self.deferred_residual else None,
                 delta2=torch.zeros(Mp, D, device=dev, dtype=act) if self.deferred_residual else None, pending=0,
                 qkv=[torch.zeros(Mp, 3 * D, device=dev, dtype=act) for _ in range(keep_layers)])
+            if H:
+                ws["x12"] = torch.zeros(Mp, 2 * H, device=dev, dtype=act)
+                ws["hidden"] = torch.zeros(Mp, (H + 31) // 32 * 32, device=dev, dtype=act)
             if need_h8:
                 ws["h8"] = torch.zeros(Mp, D, device=dev, dtype=torch.uint8)
             if need_u8:
@@ -602,7 +617,15 @@ class VisionTransformer(RuntimeStateMixin, nn.Module):
             return
         capi.attention_fwd(qkv, ws["mix"], n, self.tokens, self.heads)
         self._residual(ws, ws["mix"], bp["w_out"], bp["b_out"], M, spare_cus=sp_out, spare_if_free=free)
-        if pl["fc"] == "fp8" and pl["proj"] == "bf16":
+        if "w_12" in bp:
+            # SwiGLU: both halves of the gate from one GEMM, the gate in a pass of its own (read x12 once, write hidden),
+            # then w3 as the block's second residual branch.  Row-major throughout; bf16 or f32 operands only.
+            H = self.ffn_hidden
+            self._ln(ws, bp["ln2"], M, store=False)
+            capi.gemm(ws["h"], bp["w_12"], ws["x12"], bp["b_12"], capi.EPI_BIAS, m=M, stream_out=so["fc"], spare_cus=sp_fc, spare_if_free=free)
+            capi.swiglu_fwd(ws["x12"][:M], ws["hidden"][:M, :H])
+            self._residual(ws, ws["hidden"], bp["w_3"], bp["b_3"], M, spare_cus=sp_proj, spare_if_free=free)
+        elif pl["fc"] == "fp8" and pl["proj"] == "bf16":
             # c_fc on e4m3 operands with a bf16 `u`, which c_proj reads as the bf16 path does
             self._ln(ws, bp["ln2"], M, store=False, q=f8["h2_inv"])
             capi.gemm_fp8(ws["h8"], bp["w_fc8"], ws["u"], f8["cs_fc"], bp["b_fc"], self.act_epilogue, m=M,

@@ -32,10 +32,35 @@ ARCHS = {
     "dinov2_vitb14": (224, 14, 768, 12, 12, 0),
     "dino_tiny": (28, 14, 128, 2, 2, 0),
     "dino_w768": (28, 14, 768, 2, 12, 0),  # dino_tiny's 5 tokens per frame at a width the fp8 GEMM serves (K % 256 == 0, K >= 768)
+    # the other factories of the reference's dinov2/models/vision_transformer.py: vit_small, vit_large, vit_giant2 (whose
+    # feed-forward is the SwiGLU of `DINO_FFN`), and their test geometries
+    "dinov2_vits14": (224, 14, 384, 12, 6, 0),
+    "dinov2_vitl14": (224, 14, 1024, 24, 16, 0),
+    "dinov2_vitg14": (224, 14, 1536, 40, 24, 0),
+    "dino_tiny_swiglu": (28, 14, 128, 2, 2, 0),  # dino_tiny with the SwiGLU feed-forward (H = 344: no multiple of 64)
+    "dino_s2": (28, 14, 384, 2, 6, 0),  # ViT-S/14's width and heads, 5 tokens, two layers
+    "dino_g2": (224, 14, 1536, 2, 24, 0),  # ViT-g/14's width, heads, feed-forward (H = 4096) and 257 tokens, two layers
 }
 # ... and the image size their `pos_embed` is stored for (518 px = a 37x37 grid, resampled to the run's grid; the test
 # geometries 70 px = 5x5 -> 2x2)
-DINO_IMG_SIZE = {"dinov2_vitb14": 518, "dino_tiny": 70, "dino_w768": 70}
+DINO_IMG_SIZE = {"dinov2_vitb14": 518, "dino_tiny": 70, "dino_w768": 70, "dinov2_vits14": 518, "dinov2_vitl14": 518, "dinov2_vitg14": 518,
+                 "dino_tiny_swiglu": 70, "dino_s2": 70, "dino_g2": 518}
+# ... and their feed-forward: "mlp" = fc1 -> GELU -> fc2 with 4 x width hidden channels; "swiglu" = the reference's
+# `ffn_layer="swiglufused"` (dinov2/layers/swiglu_ffn.py): w12 -> silu(x1) * x2 -> w3 with `swiglu_hidden(width)` channels
+DINO_FFN = {name: "swiglu" if name in ("dinov2_vitg14", "dino_tiny_swiglu", "dino_g2") else "mlp" for name in DINO_IMG_SIZE}
+
+# The towers by the names of the published model cards (facebook/dinov2-small / -base / -large / -giant): what a config may
+# carry in `architecture` beside a key of `DINO_IMG_SIZE`.  For ViT-L/14 it is the ONLY spelling `model_arch` takes: that
+# `architecture: dinov2_vitl14` is refused under this foundation is pinned behaviour from before the tower existed
+# (tests/test_dinov2_cpu.py), and it stays.
+DINO_ALIASES = {"dinov2-small": "dinov2_vits14", "dinov2-base": "dinov2_vitb14", "dinov2-large": "dinov2_vitl14", "dinov2-giant": "dinov2_vitg14"}
+DINO_ALIAS_ONLY = ("dinov2_vitl14",)
+
+
+def swiglu_hidden(width):
+    """Hidden channels of `SwiGLUFFNFused(in_features=width, hidden_features=4 * width)`: two thirds of the MLP's, rounded up to
+    a multiple of 8 (1536 -> 4096, 128 -> 344)."""
+    return (int(4 * width * 2 / 3) + 7) // 8 * 8
 
 
 # the model names the reference's `clip.load` knows (src/clip/clip.py:30-40): what a reference config carries in `architecture`
@@ -46,16 +71,23 @@ def model_arch(config):
     """The `ARCHS` row a config runs on.  With `foundation: dinov2` the reference ignores `architecture` and builds
     ViT-B/14 (src/models.py:441-444), and its shipped dino configs still carry `architecture: ViT-B/16`.  So here: one
     of the reference's CLIP model names (or no entry) is ignored in the same way; the name of a DINOv2 geometry of
-    `DINO_IMG_SIZE` selects it (`dino_tiny` for tests); anything else -- this project's CLIP test geometries such as
+    `DINO_IMG_SIZE` or a model-card name of `DINO_ALIASES` selects it (`dino_tiny` for tests; ViT-L/14 by its alias only); anything else -- this project's CLIP test geometries such as
     "tiny" -- is refused, rather than answered with an 86 M-parameter ViT-B/14 nobody named."""
     if "foundation" in config and config.foundation == "dinov2":
         name = config.architecture if "architecture" in config else None
-        if name in DINO_IMG_SIZE:
+        if name in DINO_ALIASES:
+            return DINO_ALIASES[name]
+        if name in DINO_IMG_SIZE and name not in DINO_ALIAS_ONLY:
             return name
         if name is None or name in REFERENCE_CLIP_NAMES:
             return "dinov2_vitb14"
+        if name in DINO_ALIAS_ONLY:
+            alias = next(a for a, n in DINO_ALIASES.items() if n == name)
+            raise NotImplementedError(f"foundation 'dinov2' with architecture {name!r}: that spelling has always been refused here and "
+                                      f"stays so; the tower is built, name it architecture: {alias!r}")
         raise NotImplementedError(f"foundation 'dinov2' with architecture {name!r}: no DINOv2 tower of that geometry is built "
-                                  f"(built: {sorted(DINO_IMG_SIZE)}; the reference's CLIP model names are ignored, as in the reference)")
+                                  f"(built: {sorted(n for n in DINO_IMG_SIZE if n not in DINO_ALIAS_ONLY) + sorted(DINO_ALIASES)}; "
+                                  "the reference's CLIP model names are ignored, as in the reference)")
     return config.architecture
 
 
@@ -79,10 +111,17 @@ def dinov2_schema(arch):
         s[p + "ls1.gamma"] = (width,)
         s[p + "norm2.weight"] = (width,)
         s[p + "norm2.bias"] = (width,)
-        s[p + "mlp.fc1.weight"] = (4 * width, width)
-        s[p + "mlp.fc1.bias"] = (4 * width,)
-        s[p + "mlp.fc2.weight"] = (width, 4 * width)
-        s[p + "mlp.fc2.bias"] = (width,)
+        if DINO_FFN[arch] == "swiglu":
+            H = swiglu_hidden(width)
+            s[p + "mlp.w12.weight"] = (2 * H, width)
+            s[p + "mlp.w12.bias"] = (2 * H,)
+            s[p + "mlp.w3.weight"] = (width, H)
+            s[p + "mlp.w3.bias"] = (width,)
+        else:
+            s[p + "mlp.fc1.weight"] = (4 * width, width)
+            s[p + "mlp.fc1.bias"] = (4 * width,)
+            s[p + "mlp.fc2.weight"] = (width, 4 * width)
+            s[p + "mlp.fc2.bias"] = (width,)
         s[p + "ls2.gamma"] = (width,)
     s["backbone.norm.weight"] = (width,)
     s["backbone.norm.bias"] = (width,)
@@ -243,7 +282,9 @@ def resolve_layer_indices(config, n_layers):
 def random_state_dict(config, num_frames, seed=0):
     """Seeded fp32 `Detector` state_dict (reference key names).  The decoder's ln_1 / ln_2 /
     mlp start as copies of encoder layer `layer_indices[i]`, as the reference's
-    `_apply_reference` does (`src/models.py:226-229`, concat_ref == 0)."""
+    `_apply_reference` does (`src/models.py:226-229`, concat_ref == 0).  A SwiGLU tower has no fc1 / fc2 to copy (the
+    reference's `fetch_mlp_params` maps those two names only, and a decoder block is always c_fc -> QuickGELU -> c_proj):
+    there the decoder's mlp keeps its own seeded fill and only the two LayerNorms are copies."""
     arch = model_arch(config)
     dino = "foundation" in config and config.foundation == "dinov2"
     res, patch, width, layers, heads, _ = ARCHS[arch]
@@ -266,6 +307,8 @@ def random_state_dict(config, num_frames, seed=0):
             for part in ("ln_1.weight", "ln_1.bias", "ln_2.weight", "ln_2.bias", "mlp.c_fc.weight",
                          "mlp.c_fc.bias", "mlp.c_proj.weight", "mlp.c_proj.bias"):
                 src = f"encoder.transformer.resblocks.{l}.{part}"
+                if dino and DINO_FFN[arch] == "swiglu" and part.startswith("mlp."):
+                    continue
                 if dino:  # norm1 / norm2 / mlp.fc1 / mlp.fc2 of the backbone's block (reference src/models.py:192-209)
                     theirs = part
                     for a_, b_ in (("ln_1", "norm1"), ("ln_2", "norm2"), ("c_fc", "fc1"), ("c_proj", "fc2")):
