@@ -28,8 +28,9 @@ FLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-
 # offsets and weights per lane across its frame loop (both instantiations are checked).  yuv.hip's two kernels (both names
 # hold "yuv420_") are byte movers as well: the converter keeps six 8-byte results per lane, the fused gather align.hip's state.
 # swiglu.hip's gate kernels (every instantiation holds "swiglu_") move three elements per result and nothing else.
+# kv_gather.hip's row gathers ("kv_gather_": both forms, every instantiation) move two rows per lane and nothing else.
 NO_SCRATCH = {"gemm256e.hip": "gemm256e_kernel", "attention_mfma_xrow.hip": "attn_mfma_xrow_kernel", "align.hip": "align_crop_u8_kernel",
-              "elastic.hip": "elastic_remap_u8_kernel", "yuv.hip": "yuv420_", "swiglu.hip": "swiglu_"}
+              "elastic.hip": "elastic_remap_u8_kernel", "yuv.hip": "yuv420_", "swiglu.hip": "swiglu_", "kv_gather.hip": "kv_gather_"}
 
 
 def _hipcc():
@@ -81,6 +82,7 @@ def build(force=False, verbose=False, extra_flags=()):
     headers.append(os.path.join(INCLUDE, "dfdclip_elastic.h"))
     headers.append(os.path.join(INCLUDE, "dfdclip_yuv.h"))
     headers.append(os.path.join(INCLUDE, "dfdclip_swiglu.h"))
+    headers.append(os.path.join(INCLUDE, "dfdclip_kvgather.h"))
     headers.append(os.path.join(INCLUDE, "dfdclip_hooks.h"))
     jobs, objs = [], []
     for src in sources():

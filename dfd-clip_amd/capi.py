@@ -227,6 +227,15 @@ SWIGLU_SIGNATURES = {
     "dfd_swiglu_last_path": (c_int, []),
 }
 
+KVGATHER_VEC16, KVGATHER_ELEMENT = 1, 2  # dfd_kv_gather_last_path: 16-byte accesses, or element by element
+
+# the K/V row gather of patch-masked training beside the ABI, in a header of its own (include/dfdclip_kvgather.h)
+KVGATHER_SIGNATURES = {
+    "dfd_kv_gather_patches": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                      c_int64, c_int, c_int, c_int, c_int, c_void_p]),
+    "dfd_kv_gather_last_path": (c_int, []),
+}
+
 # test / measurement hooks outside the ABI header (include/dfdclip_hooks.h)
 class AttentionPlan(Structure):
     """dfd_attention_plan_t (include/dfdclip_hooks.h)."""
@@ -284,7 +293,8 @@ def load_library(path=None):
         raise DfdError(f"{path} not found: the HIP kernel library is not built and there is no fallback path")
     lib = ctypes.CDLL(path)
     for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **EXPLAIN_SIGNATURES, **AUGMENT_SIGNATURES, **ALIGN_SIGNATURES,
-                               **ELASTIC_SIGNATURES, **YUV_SIGNATURES, **SWIGLU_SIGNATURES, **HOOK_SIGNATURES}.items():
+                               **ELASTIC_SIGNATURES, **YUV_SIGNATURES, **SWIGLU_SIGNATURES, **KVGATHER_SIGNATURES,
+                               **HOOK_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError:
@@ -543,6 +553,56 @@ def swiglu_fwd(x12, hidden):
 def swiglu_last_path():
     """SWIGLU_VEC16 / SWIGLU_ELEMENT: the form the last `swiglu_fwd` of this thread launched (0: none, or a no-op)."""
     return load_library().dfd_swiglu_last_path()
+
+
+def kv_gather_patches(k, v, index, pos, k_out=None, v_out=None, T=1, P=None, index_host=None):
+    """k_out[l, f*S + j] = k[l, f, index[l, j]] (+ pos[f % T]), the same for v (include/dfdclip_kvgather.h): the kept patch rows
+    of patch-masked training, K and V of every tapped layer in one launch.
+
+    k, v: two views of one layout, bf16 or f32 — 4-D [L, frames, P, D] with unit column stride and any other strides (the
+    views `extract_kv(in_place=)` returns), or contiguous 3-D [L, frames*P, D] with `P=` given.  index: device int32 [L, S].
+    pos: device f32 [T, D] or None.  k_out / v_out: contiguous [L, frames*S, D] of the sources' dtype, allocated when None.
+    Raises before the launch when the table has an entry outside [0, P) (the kernel would clamp it): `index_host` is the
+    host copy to look at — without it the device table is copied back, which synchronises.  Returns (k_out, v_out)."""
+    _dev(k, v, index, pos, k_out, v_out)
+    assert k.dtype == v.dtype and k.dtype in _DTYPE, (k.dtype, v.dtype)
+    assert k.shape == v.shape and k.stride() == v.stride(), "k and v are two views of one layout"
+    if k.dim() == 4:
+        L, frames, P_, D = k.shape
+        assert P is None or P == P_, (P, P_)
+        assert k.stride(3) == 1 or D <= 1, "rows are dense: unit column stride"
+        s_layer, s_frame, s_patch = k.stride(0), k.stride(1), k.stride(2)
+    else:
+        assert k.dim() == 3 and k.is_contiguous() and v.is_contiguous() and P is not None and P > 0 and k.shape[1] % P == 0, (k.shape, P)
+        L, D, P_ = k.shape[0], k.shape[2], int(P)
+        frames = k.shape[1] // P_
+        s_layer, s_frame, s_patch = frames * P_ * D, P_ * D, D
+    # (a dimension of size 1 may carry any stride in torch; the ABI wants stride_patch >= D whatever the sizes)
+    s_patch = max(s_patch, D)
+    assert index.dtype == torch.int32 and index.dim() == 2 and index.shape[0] == L and index.is_contiguous(), (index.shape, index.dtype, L)
+    S = index.shape[1]
+    host = index.cpu() if index_host is None else index_host
+    assert tuple(host.shape) == (L, S), (host.shape, L, S)
+    if host.numel() and (int(host.min()) < 0 or int(host.max()) >= P_):
+        raise DfdError(f"kv_gather_patches: the index table has an entry outside [0, {P_}) (min {int(host.min())}, max {int(host.max())})")
+    if pos is not None:
+        assert pos.dtype == torch.float32 and pos.is_contiguous() and tuple(pos.shape) == (T, D), (pos.shape, pos.dtype, T, D)
+    if k_out is None:
+        k_out = torch.empty(L, frames * S, D, device=k.device, dtype=k.dtype)
+    if v_out is None:
+        v_out = torch.empty(L, frames * S, D, device=k.device, dtype=k.dtype)
+    for o in (k_out, v_out):
+        assert tuple(o.shape) == (L, frames * S, D) and o.dtype == k.dtype and o.is_contiguous(), (o.shape, o.dtype)
+    if k_out.numel() == 0:
+        return k_out, v_out  # (an empty tensor has no address to hand over; the ABI's no-op)
+    _check(load_library().dfd_kv_gather_patches(_ptr(k), _ptr(v), _DTYPE[k.dtype], s_layer, s_frame, s_patch, _ptr(index), _ptr(pos),
+                                                _ptr(k_out), _ptr(v_out), L, frames, int(T), P_, S, D, _stream()), "dfd_kv_gather_patches")
+    return k_out, v_out
+
+
+def kv_gather_last_path():
+    """KVGATHER_VEC16 / KVGATHER_ELEMENT: the form the last `kv_gather_patches` of this thread launched (0: none, or a no-op)."""
+    return load_library().dfd_kv_gather_last_path()
 
 
 def profile_gemm(epilogue=None):

@@ -644,6 +644,11 @@ class _DecoderFn(torch.autograd.Function):
             feat, saved = ent["feat"].clone(), ent["saved"]
         else:
             raws, feat, outs, saved = dec._forward_kernels(w, k_all, v_all, mask, B, T, P, save=True, drop_rng=drop_rng, kv_pos=kv_pos)
+            # The node must not hold its own OUTPUTS: ctx -> saved -> feat -> grad_fn -> ctx is a cycle that runs through
+            # the autograd node, which Python's collector cannot see — every eager training step then kept its activations
+            # and its K/V for good (0.4 GiB per patch-masked step at B16xT30, 2 GiB with an adapter).  Aliases without a
+            # grad_fn carry the same values.
+            saved = dict(saved, feat=feat.detach(), raws=[r.detach() for r in raws])
         ctx.graph_entry = ent
         ctx.after_backward, dec._after_backward = dec._after_backward, None
         ctx.dec, ctx.w, ctx.saved, ctx.dims, ctx.names = dec, w, saved, dims, names

@@ -40,6 +40,39 @@ _ENC_STREAMS = {}  # device -> the process's high-priority encoder stream (`Dete
 CLIP_CACHE = os.path.expanduser("~/.cache/clip")  # where the reference's downloader leaves checkpoints (clip/clip.py:94)
 
 
+def draw_patch_indices(kind, patches, num_select, layer_indices, guide_v, out):
+    """The kept patch positions of one patch-masked step, drawn on the host with the reference's calls in its order
+    (`src/models.py:511-544`): "batch" draws once for all tapped layers, "sample" and "guide" once per layer ("guide" with
+    the layer's attention map `guide_v[layer]` as the probabilities).  Row i of `out` (int array [L, num_select]) receives
+    layer i's positions.  The numpy stream advances exactly as it does in the per-layer loop of `mask_gather="torch"`."""
+    idx = None
+    for i, layer in enumerate(layer_indices):
+        if kind == "guide":
+            idx = np.random.choice(range(patches), num_select, replace=False, p=guide_v[layer].flatten())
+        elif idx is None or kind == "sample":
+            idx = np.random.choice(range(patches), num_select, replace=False)
+        out[i] = idx
+    return out
+
+
+def gather_reference(k, v, index, pos, T, P=None):
+    """What `capi.kv_gather_patches` computes, in plain torch on any device (the yardstick of its tests):
+    out[l, f*S + j] = src[l, f, index[l, j]] (+ pos[f % T] rounded to the tensors' dtype first, then one add).
+    k, v: [L, frames, P, D] views, or [L, frames*P, D] with `P=`; index: integer [L, S]; pos: f32 [T, D] or None.
+    -> (k_out, v_out), contiguous [L, frames*S, D]."""
+    outs = []
+    for src in (k, v):
+        if src.dim() == 3:
+            src = src.reshape(src.shape[0], src.shape[1] // P, P, src.shape[2])
+        L, F, _, D = src.shape
+        S = index.shape[1]
+        rows = torch.stack([src[l].index_select(1, index[l].long()).reshape(F * S, D) for l in range(L)]) if L else src.new_empty(0, F * S, D)
+        if pos is not None:
+            rows = (rows.view(L, F // T, T, S, D) + pos.to(rows.dtype).view(1, 1, T, 1, D)).view(L, F * S, D)
+        outs.append(rows.contiguous())
+    return outs[0], outs[1]
+
+
 class TaskLoss:
     """Unreduced loss of one task head: `loss(logits [B, out_dim], labels) -> [B]`.  The trainer takes the mean itself
     (reference `src/trainer.py:154-155`); the config names a loss by the reference's factory name, optionally with
@@ -212,7 +245,7 @@ class ClipTransform:
 
 class Detector(RuntimeStateMixin, nn.Module):
     _RUNTIME_STATE = {"_kv_static": None, "_kv_cache": {}, "_enc_stream": None, "_pipe_events": [[], []], "_pipe_step": 0, "_pos_snap": None,
-                      "_drop_master": None, "_enc_graphs": {}, "_enc_graph_seen": {}, "_enc_graphs_failed": None, "_all_params": None}
+                      "_mask_tables": None, "_mask_step": 0, "_last_masked_kv": None, "_last_masked_src": None, "_drop_master": None, "_enc_graphs": {}, "_enc_graph_seen": {}, "_enc_graphs_failed": None, "_all_params": None}
 
     def _apply(self, fn, *a, **k):
         self._all_params = None  # (.to() / .half() may re-create parameter objects)
@@ -310,6 +343,13 @@ class Detector(RuntimeStateMixin, nn.Module):
         self._pipe_events = [[], []]
         self._pipe_step = 0
         self._pos_snap = None
+        # `train_mode.patch_mask`: how the kept rows are gathered.  "device" = one dfd_kv_gather_patches launch behind
+        # `_encode` (`_masked_kv_device`), "torch" = per-layer index_select / stack / add on the dense export (the A/B arm)
+        self.mask_gather = "device"
+        self._last_mask_path = None
+        self._mask_tables, self._mask_step = None, 0
+        self._keep_masked_kv = False  # tests: keep what a masked forward gathered in `_last_masked_kv`, and from where in `_last_masked_src`
+        self._last_masked_kv = self._last_masked_src = None
         # train-mode dropout (reference models.py:163, :294, :304, :804-912; every configs/deepfake/*.yaml sets 0.5):
         # counter-based masks from a device-resident {seed, step}; see `seed_dropout`
         self.dropout_p = float(config.dropout) if "dropout" in config else 0.0
@@ -567,6 +607,61 @@ class Detector(RuntimeStateMixin, nn.Module):
         g.replay()
         return True
 
+    @property
+    def last_mask_path(self):
+        """"device" or "torch": the arm the last patch-masked forward took (None: there was none yet).  For tests."""
+        return self._last_mask_path
+
+    def _mask_table(self, patches, num_select, device):
+        """This step's kept positions -> (pinned int32 [L, S] table, its device copy).  The draws stay on the host (the numpy
+        stream is the reference's); all L rows travel in ONE non-blocking copy on the caller's stream.  Two pinned slots
+        alternate, each guarded by an event recorded behind its copy: the host waits for it before it rewrites the slot,
+        so a table whose copy is still in flight is never touched (in practice the copy of two steps ago is long done)."""
+        shape = (len(self.layer_indices), num_select)
+        if self._mask_tables is None or tuple(self._mask_tables[0][0].shape) != shape:
+            for _, ev in self._mask_tables or ():
+                ev.synchronize()
+            self._mask_tables = [(torch.empty(shape, dtype=torch.int32).pin_memory(), torch.cuda.Event()) for _ in range(2)]
+            self._mask_step = 0
+        host, ev = self._mask_tables[self._mask_step % 2]
+        self._mask_step += 1
+        ev.synchronize()
+        draw_patch_indices(self.train_mode.patch_mask.type, patches, num_select, self.layer_indices,
+                           None if self.guide_map is None else self.guide_map["v"], host.numpy())
+        dev = host.to(device, non_blocking=True)
+        ev.record()
+        return host, dev
+
+    def _masked_kv_device(self, x, t, pos, drop_rng):
+        """Patch-masked training on the fast path (models.py:511-544) -> the (k, v) the decoder reads, [L, B*T*S, D].
+
+        The encoder pass goes through `_encode` like an unmasked one — K/V in place (no export written), persistent sets,
+        the pipelined stream and the encoder graph when those are on — and ONE `dfd_kv_gather_patches` launch on the
+        caller's stream then copies the kept rows of every tapped layer out of the q|k|v buffers (or out of the dense
+        export with `kv_in_place = False`).  Without an adapter it adds the positional embedding on the way: the live
+        parameter, read on the caller's stream, which is ordered after the previous optimizer step.  `keep=True`: nothing
+        but the gather reads the set, and the gather is ordered before the next pass into it by stream order or, when
+        pipelined, by the set's events — all three are recorded right behind the gather, because neither the decoder nor
+        the adapter nor their backward passes read the set in this mode."""
+        self._last_mask_path = "device"
+        patches = (self.encoder.input_resolution // self.encoder.patch_size) ** 2
+        num_select = int(patches * self.train_mode.patch_mask.ratio)
+        host, index = self._mask_table(patches, num_select, x.device)
+        src, pipe = self._encode(x, t, None, keep=True, allow_in_place=bool(self.kv_in_place))
+        kr, vr = capi.kv_gather_patches(src[0], src[1], index, pos if self.adapter is None else None, T=t, P=patches, index_host=host)
+        if pipe is not None:
+            for ev in pipe[1:]:
+                ev.record(pipe[0])
+        if self._keep_masked_kv:
+            self._last_masked_kv, self._last_masked_src = (kr, vr), (src[0], src[1])
+        if self.adapter is None:
+            return kr, vr
+        self.adapter.patches = num_select
+        try:
+            return self.adapter.run(kr, vr, t, pos, drop_rng)
+        finally:
+            self.adapter.patches = patches
+
     def predict(self, x, m, with_video_features=False, with_adapt_features=False, train=False, with_attention=False):
         """x [B,T,3,R,R], m [B,T] bool -> (task_logits list of [B,out_dim] with L2 norm 5, features).
         `with_attention`: features["attention"] = per tapped layer the f32 [B, heads, T, patches] weight that the decoder
@@ -588,7 +683,12 @@ class Detector(RuntimeStateMixin, nn.Module):
         if self.adapter is None and not masked:
             self.decoder.use_graphs = bool(self.static_graphs and train)
             kv, pipe = self._encode(x, t, pos, keep=bool(self.static_graphs and train))
+        elif masked and self.mask_gather == "device":
+            kv = self._masked_kv_device(x, t, pos, drop_rng)
         elif masked:
+            if self.mask_gather != "torch":
+                raise ValueError(f"mask_gather={self.mask_gather!r}: 'device' or 'torch'")
+            self._last_mask_path = "torch"
             # keep a random subset of patch positions per layer (models.py:511-544): "batch" draws once for all
             # layers, "sample" per layer.  The raw export is row-gathered, then adapter / positional add follow.
             kr, vr = self.encoder.extract_kv(x.flatten(0, 1), self.layer_indices, t, None)
@@ -605,6 +705,8 @@ class Detector(RuntimeStateMixin, nn.Module):
                 vs.append(vr[i].view(b * t, P, -1).index_select(1, idx).reshape(b * t * num_select, -1))
             kr, vr = torch.stack(ks), torch.stack(vs)
             if self.adapter is not None:
+                if self._keep_masked_kv:
+                    self._last_masked_kv = (kr, vr)
                 self.adapter.patches = num_select
                 try:
                     kv = self.adapter.run(kr, vr, t, pos, drop_rng)
@@ -616,6 +718,8 @@ class Detector(RuntimeStateMixin, nn.Module):
                     kr = (kr.view(len(ks), b, t, num_select, -1) + pp).view_as(kr)
                     vr = (vr.view(len(vs), b, t, num_select, -1) + pp).view_as(vr)
                 kv = (kr.contiguous(), vr.contiguous())
+                if self._keep_masked_kv:
+                    self._last_masked_kv = kv
         else:
             # raw K/V export, then adapter(kv) + pos (models.py:546-549, :326-329); differentiable w.r.t. the
             # adapter's parameters when they are trainable
