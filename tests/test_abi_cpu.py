@@ -86,6 +86,81 @@ def test_decoder_attention_entry_points_refuse_the_same_arguments(lib):
         assert call(name, B=0, dt=capi.BF16, lay=capi.KvLayoutDesc(D + 8, (P + 1) * (D + 8), p)) == 0, (name, lib.dfd_last_error())
 
 
+def test_layernorm_entry_points_refuse_the_same_arguments(lib):
+    """The six LayerNorm entry points share one argument check (csrc/layernorm.hip ln_check): each refuses every bad
+    argument of the table that applies to it on the host, under its own name and with the rule's key phrase, and accepts
+    the valid call with rows = 0.  Fake aligned addresses; no pointer is dereferenced."""
+    X, G, B, GA, BA, D, D2, Y, Y8 = ((i + 1) << 12 for i in range(9))
+    F32, BF16, FP8 = capi.F32, capi.BF16, capi.FP8
+    plain, two, add = ("dfd_layernorm", "dfd_layernorm_dual"), ("dfd_layernorm2", "dfd_layernorm2_dual"), ("dfd_add_layernorm", "dfd_add_layernorm_dual")
+    single, dual = (plain[0], two[0], add[0]), (plain[1], two[1], add[1])
+    everyone = plain + two + add
+
+    def call(name, x=X, ldx=768, g=G, ga=GA, d=D, d2=D2, ldd=768, ddt=BF16, y=Y, ldy=768, ydt=BF16, y8=Y8, ldy8=768, rows=0, cols=768,
+             scale=None):
+        if scale is None:
+            scale = 0.5 if name in dual or ydt == FP8 else 0.0
+        front = {plain: (x, ldx, g, B), two: (x, ldx, ga, BA, g, B), add: (x, ldx, d, d2, ldd, ddt, 1, g, B)}[
+            next(k for k in (plain, two, add) if name in k)]
+        out = (y, ldy, y8, ldy8) if name in dual else (y, ldy, ydt)
+        return getattr(lib, name)(*front, *out, rows, cols, 1e-5, scale, None)
+
+    bad = [  # (what, arguments, key phrase, the entry points it applies to)
+        ("null x", dict(x=None), "null pointer", everyone),
+        ("cols = 6", dict(cols=6, ldx=8, ldy=8, ldy8=8, ldd=8), "multiple of 4", everyone),
+        ("cols = 0", dict(cols=0), "multiple of 4", everyone),
+        ("cols = 2052", dict(cols=2052, ldx=2052, ldy=2052, ldy8=2052, ldd=2052), "multiple of 4", two + add),
+        ("cols = 4100", dict(cols=4100, ldx=4100, ldy=4100, ldy8=4100, ldd=4100), "multiple of 4", everyone),
+        ("ldx < cols", dict(ldx=764), "bad leading dimension", everyone),
+        ("ldx % 4 != 0", dict(ldx=770), "bad leading dimension", everyone),
+        ("ldy < cols", dict(ldy=764), "bad leading dimension", everyone),
+        ("ldy8 % 4 != 0", dict(ldy8=770), "bad leading dimension", dual),
+        ("ldd < cols", dict(ldd=764), "bad leading dimension", add),
+        ("x off by 8 bytes", dict(x=X + 8), "aligned", everyone),
+        ("gamma off by 8 bytes", dict(g=G + 8), "aligned", everyone),
+        ("gamma_a off by 8 bytes", dict(ga=GA + 8), "aligned", two),
+        ("y off by 4 bytes", dict(y=Y + 4), "aligned", everyone),
+        ("e4m3 y off by 2 bytes", dict(y=Y + 2, ydt=FP8), "aligned", single),
+        ("y8 off by 2 bytes", dict(y8=Y8 + 2), "aligned", dual),
+        ("delta off by 4 bytes", dict(d=D + 4), "aligned", add),
+        ("delta2 off by 4 bytes", dict(d2=D2 + 4), "aligned", add),
+        ("f32 delta off by 4 bytes", dict(d=D + 4, ddt=F32), "aligned", add),
+        ("e4m3 without a scale", dict(ydt=FP8, scale=0.0), "inv_scale > 0", single),
+        ("e4m3 with a negative scale", dict(ydt=FP8, scale=-1.0), "inv_scale > 0", single),
+        ("dual without a scale", dict(scale=0.0), "inv_scale > 0", dual),
+        ("y_dtype = 7", dict(ydt=7), "y_dtype", single),
+        ("delta_dtype = 7", dict(ddt=7), "delta_dtype", add),
+        ("y is x", dict(y=X), "must not alias", everyone[1:]),
+        ("y8 is x", dict(y8=X), "must not alias", dual),
+        ("y is delta", dict(y=D), "must not alias", add),
+        ("y8 is delta2", dict(y8=D2), "must not alias", add[1:]),
+        ("y16 is y8", dict(y8=Y), "must not alias", dual),
+        ("rows = 2^34", dict(rows=1 << 34), "fit a grid", everyone),
+        ("rows = 4 (2^31 - 1) + 1", dict(rows=4 * (2 ** 31 - 1) + 1), "fit a grid", everyone),
+        ("rows = -1", dict(rows=-1), "rows=-1", everyone),
+    ]
+    for name in everyone:
+        for what, kw, phrase, applies in bad:
+            if name not in applies:
+                continue
+            assert call(name, **kw) == -1, f"{name}: {what} was accepted"
+            err = lib.dfd_last_error()
+            assert err.startswith(name.encode() + b":") and phrase.encode() in err, (name, what, err)
+        assert call(name) == 0, (name, lib.dfd_last_error())
+        # the widest row of each kind, padded rows, and the alignments that are enough: 8 bytes for an f32 y, 4 for e4m3
+        wide = 4096 if name in plain else 2048
+        assert call(name, cols=wide, ldx=wide + 4, ldy=wide + 8, ldy8=wide + 4, ldd=wide + 12) == 0, (name, lib.dfd_last_error())
+        assert call(name, y8=Y8 + 4) == 0, (name, lib.dfd_last_error())
+        if name in single:
+            assert call(name, y=Y + 8, ydt=F32) == 0 and call(name, y=Y + 4, ydt=FP8) == 0, (name, lib.dfd_last_error())
+        if name in add:
+            assert call(name, d2=None) == 0 and call(name, ddt=F32, d=D + 8, d2=D2 + 8) == 0, (name, lib.dfd_last_error())
+    # what dfd_layernorm alone accepts: f32 in place (encoder.py's use); and the plain kind's 16 slabs
+    assert call("dfd_layernorm", y=X, ydt=F32) == 0, lib.dfd_last_error()
+    for name in plain:
+        assert call(name, cols=2052, ldx=2052, ldy=2052, ldy8=2052) == 0, (name, lib.dfd_last_error())
+
+
 def test_gemm_at_b_refuses_rows_the_fallback_cannot_launch(lib):
     """The transpose + general-kernel path of dfd_gemm_at_b puts one block of 32 rows on grid.y: more than 65535 blocks
     are refused on the host, under the function's name, before any launch.  No pointer is dereferenced and nothing is

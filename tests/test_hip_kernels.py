@@ -129,6 +129,73 @@ def test_layernorm2_is_two_layernorms(capi, rows, cols, dtype):
             capi.layernorm2(xb, ga, ba, gb, bb, xb)  # y aliasing x is refused
 
 
+@pytest.mark.parametrize("slabs", range(1, 17))
+def test_layernorm_family_every_slab_count(capi, slabs):
+    """Every slab count has its own instantiation of the three row kernels (csrc/layernorm.hip): 1..16 slabs of 256 columns
+    for the plain form, 1..8 for the others.  Each is run at a full last slab and at a ragged one where a single lane owns
+    the last slab (256 * slabs - 252 columns), on 5 rows (one workgroup and a ragged second one), against a float64
+    LayerNorm of the same inputs at the bars of test_layernorm and test_add_layernorm: f32 2e-5, bf16 1e-5 + 2^-8 |ref|.
+    The second stage of dfd_layernorm2 is held to the float64 LayerNorm of its own f32 first stage.  The dual forms write the
+    single forms' bits."""
+    rows, dev = 5, "cuda"
+
+    def ref(t, g, b):
+        return F.layer_norm(t.double(), (t.shape[1],), g.double(), b.double(), 1e-5)
+
+    def close(got, want, what):
+        atol, rtol = (2e-5, 0.0) if got.dtype == torch.float32 else (1e-5, 2 ** -8)
+        err, lim = (got.double().cpu() - want).abs(), atol + rtol * want.abs()
+        assert torch.isfinite(got.float()).all() and (err <= lim).all(), f"{what}: max err {err.max().item():.3e} over {(err / lim).max().item():.2f} of the bar"
+
+    def outputs(run, cols, scale=0.25):
+        """run(out, **kw) writes one output: f32, bf16 and e4m3 singly, then the dual pair, each from a fresh x"""
+        f32, b16 = torch.empty(rows, cols, device=dev), torch.empty(rows, cols, device=dev, dtype=torch.bfloat16)
+        e8, d16, d8 = torch.empty(rows, cols, device=dev, dtype=torch.uint8), torch.empty_like(b16), torch.empty(rows, cols, device=dev, dtype=torch.uint8)
+        xs = [run(f32), run(b16), run(e8, out_inv_scale=scale), run(d16, out8=d8, out8_inv_scale=scale)]
+        assert all(torch.equal(xs[0], t) for t in xs[1:]), "x after the call depends on the output type"
+        assert torch.equal(d16, b16) and torch.equal(d8, e8), "dual outputs differ from the single ones"
+        return xs[0], f32, b16
+
+    for cols in (256 * slabs - 252, 256 * slabs):
+        x = rnd(rows, cols, seed=70 + slabs, scale=3.0) + 0.5
+        d = rnd(rows, cols, seed=71 + slabs).to(torch.bfloat16)
+        ga, ba, g, b = (rnd(cols, seed=72 + i, scale=0.1) + (1.0 if i % 2 == 0 else 0.0) for i in range(4))
+        gad, bad, gd, bd, dd = ga.cuda(), ba.cuda(), g.cuda(), b.cuda(), d.cuda()
+
+        def plain(out, out8=None, **kw):
+            xd = x.cuda()
+            capi.layernorm(xd, gd, bd, out, **kw) if out8 is None else capi.layernorm_dual(xd, gd, bd, out, out8, **kw)
+            return xd
+
+        xd, f32, b16 = outputs(plain, cols)
+        assert torch.equal(xd.cpu(), x)
+        close(f32, ref(x, g, b), f"plain f32 cols={cols}")
+        close(b16, ref(x, g, b), f"plain bf16 cols={cols}")
+        if slabs > 8:
+            continue
+
+        def added(out, out8=None, **kw):
+            xd = x.cuda()
+            capi.add_layernorm(xd, dd, gd, bd, out, **kw) if out8 is None else capi.add_layernorm_dual(xd, dd, gd, bd, out, out8, **kw)
+            return xd
+
+        xd, f32, b16 = outputs(added, cols)
+        x_new = x + d.float()
+        assert torch.equal(xd.cpu(), x_new), "x must hold the exact fp32 sum"
+        close(f32, ref(x_new, g, b), f"add f32 cols={cols}")
+        close(b16, ref(x_new, g, b), f"add bf16 cols={cols}")
+
+        def two(out, out8=None, **kw):
+            xd = x.cuda()
+            capi.layernorm2(xd, gad, bad, gd, bd, out, **kw) if out8 is None else capi.layernorm2_dual(xd, gad, bad, gd, bd, out, out8, **kw)
+            return xd
+
+        xd, f32, b16 = outputs(two, cols)
+        close(xd, ref(x, ga, ba), f"two, first stage cols={cols}")
+        close(f32, ref(xd.cpu(), g, b), f"two f32 cols={cols}")
+        close(b16, ref(xd.cpu(), g, b), f"two bf16 cols={cols}")
+
+
 @pytest.mark.parametrize("n,res,patch", [(3, 32, 16), (5, 224, 16), (2, 224, 32), (2, 64, 8)])
 def test_patchify_strip_kernel_matches_the_general_one(capi, n, res, patch):
     """bf16 patches of 4-aligned patch sizes come from the strip kernel (whole image rows in, one contiguous run out,
