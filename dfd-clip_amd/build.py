@@ -29,8 +29,10 @@ FLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-
 # hold "yuv420_") are byte movers as well: the converter keeps six 8-byte results per lane, the fused gather align.hip's state.
 # swiglu.hip's gate kernels (every instantiation holds "swiglu_") move three elements per result and nothing else.
 # kv_gather.hip's row gathers ("kv_gather_": both forms, every instantiation) move two rows per lane and nothing else.
+# adapter.hip's kernels ("adapter_") are HBM-bound and the register-resident backward sits at the 128-VGPR ceiling of its 1024 threads.
 NO_SCRATCH = {"gemm256e.hip": "gemm256e_kernel", "attention_mfma_xrow.hip": "attn_mfma_xrow_kernel", "align.hip": "align_crop_u8_kernel",
-              "elastic.hip": "elastic_remap_u8_kernel", "yuv.hip": "yuv420_", "swiglu.hip": "swiglu_", "kv_gather.hip": "kv_gather_"}
+              "elastic.hip": "elastic_remap_u8_kernel", "yuv.hip": "yuv420_", "swiglu.hip": "swiglu_", "kv_gather.hip": "kv_gather_",
+              "adapter.hip": "adapter_"}
 
 
 def _hipcc():

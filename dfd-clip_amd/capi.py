@@ -249,7 +249,14 @@ class GemmPlan(Structure):
                 ("dynamic", c_int32)]
 
 
+class AdapterPlan(Structure):
+    """dfd_adapter_plan_t (include/dfdclip_hooks.h)."""
+    _fields_ = [("path", c_int32), ("grid", c_uint32), ("block", c_uint32), ("slabs", c_int32), ("groups_per_slab", c_int32)]
+
+
 HOOK_SIGNATURES = {
+    "dfd_adapter_norm_gelu_last_path": (c_int, []),
+    "dfd_adapter_norm_gelu_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(AdapterPlan)]),
     "dfd_gemm_last_kernel": (c_int, []),
     "dfd_gemm_plan": (c_int, [c_int, c_int, c_int, c_int64, c_int, c_int, c_int64, c_int64, c_int64, c_uint32, c_int, c_int, c_int, c_uint,
                               c_uint, c_int, POINTER(GemmPlan)]),
@@ -267,6 +274,9 @@ HOOK_SIGNATURES = {
 # kernels behind dfd_attention_fwd (DFD_ATTN_* of include/dfdclip_hooks.h, which holds the selection table)
 (ATTN_ROWS, ATTN_ROWS_CHUNKED, ATTN_ITEM7, ATTN_ITEM9, ATTN_PERSIST7_SHORT, ATTN_PERSIST7, ATTN_XROW,
  ATTN_STREAM) = range(1, 9)
+
+# kernels behind dfd_adapter_norm_gelu and the group pass of its backward (DFD_ADP_* of include/dfdclip_hooks.h)
+ADP_ROW256, ADP_JOINT_REG, ADP_JOINT, ADP_ROW = range(1, 5)
 
 # kernels behind dfd_gemm / dfd_gemm_fp8 (DFD_GEMM_* of include/dfdclip_hooks.h, which holds the selection table), and the
 # pointer bits of dfd_gemm_plan
@@ -954,6 +964,22 @@ def head_fwd(x, gamma, beta, proj, feat, raw, logits, eps=1e-5, drop=None):
 # ---- adapter structs without a LayerNorm: 768-bn, 768-xxx-768, linear (csrc/adapter_structs.hip) -----------------
 
 BN_EVAL, BN_TRAIN, BN_TRAIN_UPDATE = 0, 1, 2
+
+
+def adapter_norm_gelu_last_path():
+    """ADP_* of this thread's last adapter_norm_gelu or adapter_norm_gelu_bwd that launched a kernel; 0 = none yet."""
+    return load_library().dfd_adapter_norm_gelu_last_path()
+
+
+def adapter_norm_gelu_plan(frames, patches, x, joint, a_dtype, dtype, misaligned=False, backward=False):
+    """What adapter_norm_gelu (or, with `backward`, adapter_norm_gelu_bwd) would do with this shape: an AdapterPlan (path ADP_*,
+    grid, block, slabs, groups_per_slab).  DfdError for what the entry point refuses.  Touches no device."""
+    p = AdapterPlan()
+    rc = load_library().dfd_adapter_norm_gelu_plan(frames, patches, x, int(joint), _DTYPE[a_dtype], _DTYPE[dtype], int(bool(misaligned)),
+                                                   int(bool(backward)), ctypes.byref(p))
+    if rc < 0:
+        raise DfdError(f"dfd_adapter_norm_gelu_plan failed ({rc}): {load_library().dfd_last_error().decode()}")
+    return p
 
 
 def adapter_bn_workspace_bytes(frames, patches, width):

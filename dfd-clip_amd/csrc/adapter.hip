@@ -3,44 +3,87 @@
 // [patches, x] affine (models.py:831); "ln"/"z0" normalise each row of x (models.py:847, :860).
 // HBM-bound: one read and one write of the tensor (slab kept in registers between the passes when it
 // fits; the statistics pass re-reads from L2 otherwise).  fp32 statistics, two-pass variance.
-#include "common.hpp"
+//
+// Device side: three statistics fronts (adp_strided_stats, adp_slab_stats, adp_row256_stats: they differ in arithmetic
+// and stay apart) and the backward's dz term (adp_dz).  Host side: one call description (AdpCall), one argument check
+// (adp_check), one plan (adp_plan: which kernel, which grid) and one launch function per direction.
+#include "adapter_common.hpp"
+
+#include "../../include/dfdclip_hooks.h"
 
 namespace {
 
-__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
+// The erff form of GELU and its derivative.  gelu.hpp's gelu_erf / gelu_erf_grad (adapter_structs.hip, the GEMM epilogue)
+// go through dfd_norm_cdf and give other bits; this file's results are pinned to the erff form, so there are two.
+__device__ __forceinline__ float adp_gelu(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
+__device__ __forceinline__ float adp_gelu_grad(float z) {
+  return 0.5f * (1.0f + erff(z * 0.70710678118654752f)) + z * 0.3989422804014327f * __expf(-0.5f * z * z);
+}
 
 template <typename T> __device__ __forceinline__ float ld(const T* p) { return to_f32(*p); }
 
-template <typename T> struct Ld8;
-template <> struct Ld8<float> {
-  static __device__ __forceinline__ void load(const float* p, float* o) {
-    const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
+// The normalised quantity at element i.  gelu_first ("768-x-768" / "legacy-768-x-768", models.py:795-821):
+// y = LayerNorm(GELU(a)), so u = GELU(a) is what the statistics see; else GELU(LayerNorm(a)) and it is a itself.
+template <typename TA> __device__ __forceinline__ float adp_in(const TA* ap, int64_t i, int gelu_first) {
+  const float v = ld(ap + i);
+  return gelu_first ? adp_gelu(v) : v;
+}
+
+struct AdpStats {
+  float mean, rstd;
+};
+
+// Strided front: a thread takes elements first, first + stride, ... of the n at ap; `sum` adds across the threads that
+// share the group (a wave or the workgroup).  Adds in stride order, divides by n; the elements are read twice.
+template <typename TA, typename Stride, typename Sum>
+__device__ __forceinline__ AdpStats adp_strided_stats(const TA* ap, int gelu_first, int first, Stride stride, int n, float eps, Sum&& sum) {
+  float s = 0.f;
+  for (int i = first; i < n; i += stride) s += adp_in(ap, i, gelu_first);
+  const float mean = sum(s) / (float)n;
+  float q = 0.f;
+  for (int i = first; i < n; i += stride) { const float d = adp_in(ap, i, gelu_first) - mean; q += d * d; }
+  return AdpStats{mean, rsqrtf(sum(q) / (float)n + eps)};
+}
+
+// Register-resident front of a 1024-thread workgroup: thread tid loads chunks tid, tid + 1024, ... of 8 elements (at most
+// NCH of them, n % 8 == 0) into v ONCE and takes both statistics passes from the registers.
+template <typename TA, int NCH>
+__device__ __forceinline__ AdpStats adp_slab_stats(const TA* ap, int n, float eps, float (&v)[NCH][8], float* sc) {
+  const int tid = threadIdx.x, nchunk = n >> 3;
+  float s = 0.f;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) { o[e] = a[e]; o[4 + e] = b[e]; }
-  }
-};
-template <> struct Ld8<bf16_t> {
-  static __device__ __forceinline__ void load(const bf16_t* p, float* o) {
-    const bf16x8 a = *reinterpret_cast<const bf16x8*>(p);
+  for (int c = 0; c < NCH; ++c) {
+    const int ch = tid + c * 1024;
+    if (ch < nchunk) {
+      Vec<TA, 8>::load(ap + (int64_t)ch * 8, v[c]);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = (float)a[e];
+      for (int e = 0; e < 8; ++e) s += v[c][e];
+    }
   }
-};
-template <typename T> struct St8;
-template <> struct St8<float> {
-  static __device__ __forceinline__ void store(float* p, const float* o) {
-    *reinterpret_cast<f32x4*>(p) = f32x4{o[0], o[1], o[2], o[3]};
-    *reinterpret_cast<f32x4*>(p + 4) = f32x4{o[4], o[5], o[6], o[7]};
-  }
-};
-template <> struct St8<bf16_t> {
-  static __device__ __forceinline__ void store(bf16_t* p, const float* o) {
-    bf16x8 r;
+  const float mean = block_sum<16>(s, sc) / (float)n;
+  float q = 0.f;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) r[e] = (bf16_t)o[e];
-    *reinterpret_cast<bf16x8*>(p) = r;
-  }
-};
+  for (int c = 0; c < NCH; ++c)
+    if (tid + c * 1024 < nchunk) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { const float d = v[c][e] - mean; q += d * d; }
+    }
+  return AdpStats{mean, rsqrtf(block_sum<16>(q, sc) / (float)n + eps)};
+}
+
+// Front of a 256-wide row held by one wave, 4 elements per lane: pairwise sum, times 1/256 (not the strided front's bits).
+__device__ __forceinline__ AdpStats adp_row256_stats(const float (&v)[4], float eps) {
+  const float mean = wave_sum((v[0] + v[1]) + (v[2] + v[3])) * (1.0f / 256.0f);
+  float q = 0.f;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { const float d = v[e] - mean; q += d * d; }
+  return AdpStats{mean, rsqrtf(wave_sum(q) * (1.0f / 256.0f) + eps)};
+}
+
+// Backward: dL/dz at the affine's output z = nhat * w + b.  The LayerNorm's incoming gradient is g = adp_dz(..) * w.
+__device__ __forceinline__ float adp_dz(float dy, float nh, float w, float b, int gelu_first) {
+  return dy * (gelu_first ? 1.0f : adp_gelu_grad(nh * w + b));
+}
 
 // one workgroup per frame (joint) — slab = patches * x elements
 template <typename TA, typename T>
@@ -48,25 +91,11 @@ __global__ __launch_bounds__(1024) void adapter_nln_kernel(const TA* __restrict_
                                                            const float* __restrict__ w, const float* __restrict__ b,
                                                            int slab, float eps) {
   __shared__ float sc[16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
+  const int tid = threadIdx.x;
   const TA* ap = a + (int64_t)blockIdx.x * slab;
   T* yp = y + (int64_t)blockIdx.x * slab;
-  auto block_sum = [&](float v) {
-    v = wave_sum(v);
-    __syncthreads();
-    if (lane == 0) sc[wave] = v;
-    __syncthreads();
-    float t = 0.f;
-    for (int i = 0; i < nw; ++i) t += sc[i];
-    return t;
-  };
-  float s = 0.f;
-  for (int i = tid; i < slab; i += blockDim.x) s += ld(ap + i);
-  const float mean = block_sum(s) / (float)slab;
-  float q = 0.f;
-  for (int i = tid; i < slab; i += blockDim.x) { const float d = ld(ap + i) - mean; q += d * d; }
-  const float rstd = rsqrtf(block_sum(q) / (float)slab + eps);
-  for (int i = tid; i < slab; i += blockDim.x) yp[i] = from_f32<T>(gelu_erf((ld(ap + i) - mean) * rstd * w[i] + b[i]));
+  const auto [mean, rstd] = adp_strided_stats(ap, 0, tid, blockDim.x, slab, eps, [&](float v) { return block_sum(v, sc); });
+  for (int i = tid; i < slab; i += blockDim.x) yp[i] = from_f32<T>(adp_gelu((ld(ap + i) - mean) * rstd * w[i] + b[i]));
 }
 
 // Register-resident form of the joint ("nln") kernel: the frame's (patches, x) slab is read ONCE, 8
@@ -77,50 +106,20 @@ __global__ __launch_bounds__(1024) void adapter_nln_reg_kernel(const TA* __restr
                                                                const float* __restrict__ w, const float* __restrict__ b,
                                                                int slab, float eps) {
   __shared__ float sc[16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const TA* ap = a + (int64_t)blockIdx.x * slab;
+  const int tid = threadIdx.x, nchunk = slab >> 3;
   T* yp = y + (int64_t)blockIdx.x * slab;
-  auto block_sum = [&](float v) {
-    v = wave_sum(v);
-    __syncthreads();
-    if (lane == 0) sc[wave] = v;
-    __syncthreads();
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) t += sc[i];
-    return t;
-  };
-  const int nchunk = slab >> 3;
   float v[NCH][8];
-  float s = 0.f;
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    const int ch = tid + c * 1024;
-    if (ch < nchunk) {
-      Ld8<TA>::load(ap + (int64_t)ch * 8, v[c]);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) s += v[c][e];
-    }
-  }
-  const float mean = block_sum(s) / (float)slab;
-  float q = 0.f;
-#pragma unroll
-  for (int c = 0; c < NCH; ++c)
-    if (tid + c * 1024 < nchunk) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { const float d = v[c][e] - mean; q += d * d; }
-    }
-  const float rstd = rsqrtf(block_sum(q) / (float)slab + eps);
+  const auto [mean, rstd] = adp_slab_stats<TA, NCH>(a + (int64_t)blockIdx.x * slab, slab, eps, v, sc);
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
     const int ch = tid + c * 1024;
     if (ch < nchunk) {
       float ww[8], bb[8], o[8];
-      Ld8<float>::load(w + (int64_t)ch * 8, ww);
-      Ld8<float>::load(b + (int64_t)ch * 8, bb);
+      Vec<float, 8>::load(w + (int64_t)ch * 8, ww);
+      Vec<float, 8>::load(b + (int64_t)ch * 8, bb);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = gelu_erf((v[c][e] - mean) * rstd * ww[e] + bb[e]);
-      St8<T>::store(yp + (int64_t)ch * 8, o);
+      for (int e = 0; e < 8; ++e) o[e] = adp_gelu((v[c][e] - mean) * rstd * ww[e] + bb[e]);
+      Vec<T, 8>::store(yp + (int64_t)ch * 8, o);
     }
   }
 }
@@ -135,49 +134,15 @@ __global__ __launch_bounds__(256) void adapter_ln_kernel(const TA* __restrict__ 
   if (row >= rows) return;
   const TA* ap = a + row * x;
   T* yp = y + row * x;
-  // gelu_first ("768-x-768" / "legacy-768-x-768", models.py:795-821): y = LayerNorm(GELU(a)); else GELU(LayerNorm(a))
-  auto in = [&](int i) { const float v = ld(ap + i); return gelu_first ? gelu_erf(v) : v; };
-  float s = 0.f;
-  for (int i = lane; i < x; i += 64) s += in(i);
-  const float mean = wave_sum(s) / (float)x;
-  float q = 0.f;
-  for (int i = lane; i < x; i += 64) { const float d = in(i) - mean; q += d * d; }
-  const float rstd = rsqrtf(wave_sum(q) / (float)x + eps);
+  const auto [mean, rstd] = adp_strided_stats(ap, gelu_first, lane, 64, x, eps, [](float v) { return wave_sum(v); });
   for (int i = lane; i < x; i += 64) {
-    const float z = (in(i) - mean) * rstd * w[i] + b[i];
-    yp[i] = from_f32<T>(gelu_first ? z : gelu_erf(z));
+    const float z = (adp_in(ap, i, gelu_first) - mean) * rstd * w[i] + b[i];
+    yp[i] = from_f32<T>(gelu_first ? z : adp_gelu(z));
   }
-}
-
-__device__ __forceinline__ float gelu_erf_grad(float z) {
-  return 0.5f * (1.0f + erff(z * 0.70710678118654752f)) + z * 0.3989422804014327f * __expf(-0.5f * z * z);
 }
 
 // x == 256 fast paths of the per-row modes (0: GELU(LN(a)), 2: LN(GELU(a))): one wave per row, each lane owns 4
 // consecutive elements loaded once with one 8- or 16-byte access.
-template <typename T> struct Ld4;
-template <> struct Ld4<float> {
-  static __device__ __forceinline__ void load(const float* p, float* o) {
-    const f32x4 a = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = a[e];
-  }
-  static __device__ __forceinline__ void store(float* p, const float* o) { *reinterpret_cast<f32x4*>(p) = f32x4{o[0], o[1], o[2], o[3]}; }
-};
-template <> struct Ld4<bf16_t> {
-  static __device__ __forceinline__ void load(const bf16_t* p, float* o) {
-    const bf16x4 a = *reinterpret_cast<const bf16x4*>(p);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = (float)a[e];
-  }
-  static __device__ __forceinline__ void store(bf16_t* p, const float* o) {
-    bf16x4 r;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) r[e] = (bf16_t)o[e];
-    *reinterpret_cast<bf16x4*>(p) = r;
-  }
-};
-
 template <typename TA, typename T>
 __global__ __launch_bounds__(256) void adapter_row256_kernel(const TA* __restrict__ a, T* __restrict__ y,
                                                              const float* __restrict__ w, const float* __restrict__ b,
@@ -186,24 +151,20 @@ __global__ __launch_bounds__(256) void adapter_row256_kernel(const TA* __restric
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   float v[4], ww[4], bb[4], o[4];
-  Ld4<TA>::load(a + row * 256 + lane * 4, v);
-  Ld4<float>::load(w + lane * 4, ww);
-  Ld4<float>::load(b + lane * 4, bb);
+  Vec<TA, 4>::load(a + row * 256 + lane * 4, v);
+  Vec<float, 4>::load(w + lane * 4, ww);
+  Vec<float, 4>::load(b + lane * 4, bb);
   if (gelu_first) {
 #pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = gelu_erf(v[e]);
+    for (int e = 0; e < 4; ++e) v[e] = adp_gelu(v[e]);
   }
-  const float mean = wave_sum((v[0] + v[1]) + (v[2] + v[3])) * (1.0f / 256.0f);
-  float q = 0.f;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { const float d = v[e] - mean; q += d * d; }
-  const float rstd = rsqrtf(wave_sum(q) * (1.0f / 256.0f) + eps);
+  const auto [mean, rstd] = adp_row256_stats(v, eps);
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const float z = (v[e] - mean) * rstd * ww[e] + bb[e];
-    o[e] = gelu_first ? z : gelu_erf(z);
+    o[e] = gelu_first ? z : adp_gelu(z);
   }
-  Ld4<T>::store(y + row * 256 + lane * 4, o);
+  Vec<T, 4>::store(y + row * 256 + lane * 4, o);
 }
 
 // backward group pass for the same modes and width: da and the row's (mean, rstd)
@@ -216,23 +177,19 @@ __global__ __launch_bounds__(256) void adapter_bwd_row256_kernel(const TA* __res
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   float av[4], v[4], dd[4], ww[4], bb[4], g[4], o[4];
-  Ld4<TA>::load(a + row * 256 + lane * 4, av);
-  Ld4<T>::load(dy + row * 256 + lane * 4, dd);
-  Ld4<float>::load(w + lane * 4, ww);
-  Ld4<float>::load(b + lane * 4, bb);
+  Vec<TA, 4>::load(a + row * 256 + lane * 4, av);
+  Vec<T, 4>::load(dy + row * 256 + lane * 4, dd);
+  Vec<float, 4>::load(w + lane * 4, ww);
+  Vec<float, 4>::load(b + lane * 4, bb);
 #pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = gelu_first ? gelu_erf(av[e]) : av[e];
-  const float mean = wave_sum((v[0] + v[1]) + (v[2] + v[3])) * (1.0f / 256.0f);
-  float q = 0.f;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { const float d = v[e] - mean; q += d * d; }
-  const float rstd = rsqrtf(wave_sum(q) * (1.0f / 256.0f) + eps);
+  for (int e = 0; e < 4; ++e) v[e] = gelu_first ? adp_gelu(av[e]) : av[e];
+  const auto [mean, rstd] = adp_row256_stats(v, eps);
   float s1 = 0.f, s2 = 0.f;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const float nh = (v[e] - mean) * rstd;
     v[e] = nh;
-    g[e] = dd[e] * (gelu_first ? 1.0f : gelu_erf_grad(nh * ww[e] + bb[e])) * ww[e];
+    g[e] = adp_dz(dd[e], nh, ww[e], bb[e], gelu_first) * ww[e];
     s1 += g[e];
     s2 += g[e] * nh;
   }
@@ -240,9 +197,9 @@ __global__ __launch_bounds__(256) void adapter_bwd_row256_kernel(const TA* __res
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const float du = rstd * (g[e] - m1 - v[e] * m2);
-    o[e] = gelu_first ? du * gelu_erf_grad(av[e]) : du;
+    o[e] = gelu_first ? du * adp_gelu_grad(av[e]) : du;
   }
-  Ld4<T>::store(da + row * 256 + lane * 4, o);
+  Vec<T, 4>::store(da + row * 256 + lane * 4, o);
   if (lane == 0) { stats[2 * row] = mean; stats[2 * row + 1] = rstd; }
 }
 
@@ -254,42 +211,28 @@ __global__ __launch_bounds__(1024) void adapter_bwd_group_kernel(const TA* __res
                                                                  const float* __restrict__ b, float* __restrict__ stats,
                                                                  int group, int affine_period, float eps, int gelu_first) {
   __shared__ float sc[16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
+  const int tid = threadIdx.x;
   const TA* ap = a + (int64_t)blockIdx.x * group;
   const T* dp = dy + (int64_t)blockIdx.x * group;
   T* op = da + (int64_t)blockIdx.x * group;
-  auto block_sum = [&](float v) {
-    v = wave_sum(v);
-    __syncthreads();
-    if (lane == 0) sc[wave] = v;
-    __syncthreads();
-    float t = 0.f;
-    for (int i = 0; i < nw; ++i) t += sc[i];
-    return t;
-  };
+  const auto sum = [&](float v) { return block_sum(v, sc); };
   // gelu_first: the normalised quantity is u = GELU(a); dL/du = LN backward of dy*w, dL/da = dL/du * GELU'(a)
-  auto in = [&](int i) { const float v = ld(ap + i); return gelu_first ? gelu_erf(v) : v; };
-  float s = 0.f;
-  for (int i = tid; i < group; i += blockDim.x) s += in(i);
-  const float mean = block_sum(s) / (float)group;
-  float q = 0.f;
-  for (int i = tid; i < group; i += blockDim.x) { const float d = in(i) - mean; q += d * d; }
-  const float rstd = rsqrtf(block_sum(q) / (float)group + eps);
+  const auto [mean, rstd] = adp_strided_stats(ap, gelu_first, tid, blockDim.x, group, eps, sum);
   float s1 = 0.f, s2 = 0.f;
   for (int i = tid; i < group; i += blockDim.x) {
     const int e = i % affine_period;
-    const float nh = (in(i) - mean) * rstd;
-    const float g = ld(dp + i) * (gelu_first ? 1.0f : gelu_erf_grad(nh * w[e] + b[e])) * w[e];
+    const float nh = (adp_in(ap, i, gelu_first) - mean) * rstd;
+    const float g = adp_dz(ld(dp + i), nh, w[e], b[e], gelu_first) * w[e];
     s1 += g;
     s2 += g * nh;
   }
-  const float m1 = block_sum(s1) / (float)group, m2 = block_sum(s2) / (float)group;
+  const float m1 = sum(s1) / (float)group, m2 = sum(s2) / (float)group;
   for (int i = tid; i < group; i += blockDim.x) {
     const int e = i % affine_period;
-    const float nh = (in(i) - mean) * rstd;
-    const float g = ld(dp + i) * (gelu_first ? 1.0f : gelu_erf_grad(nh * w[e] + b[e])) * w[e];
+    const float nh = (adp_in(ap, i, gelu_first) - mean) * rstd;
+    const float g = adp_dz(ld(dp + i), nh, w[e], b[e], gelu_first) * w[e];
     const float du = rstd * (g - m1 - nh * m2);
-    op[i] = from_f32<T>(gelu_first ? du * gelu_erf_grad(ld(ap + i)) : du);
+    op[i] = from_f32<T>(gelu_first ? du * adp_gelu_grad(ld(ap + i)) : du);
   }
   if (tid == 0) { stats[2 * blockIdx.x] = mean; stats[2 * blockIdx.x + 1] = rstd; }
 }
@@ -302,76 +245,46 @@ __global__ __launch_bounds__(1024) void adapter_bwd_group_reg_kernel(const TA* _
                                                                      const float* __restrict__ b, float* __restrict__ stats,
                                                                      int group, float eps) {
   __shared__ float sc[16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const TA* ap = a + (int64_t)blockIdx.x * group;
+  const int tid = threadIdx.x, nchunk = group >> 3;
   const T* dp = dy + (int64_t)blockIdx.x * group;
   T* op = da + (int64_t)blockIdx.x * group;
-  auto block_sum = [&](float v) {
-    v = wave_sum(v);
-    __syncthreads();
-    if (lane == 0) sc[wave] = v;
-    __syncthreads();
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) t += sc[i];
-    return t;
-  };
-  const int nchunk = group >> 3;
   float v[NCH][8];
-  float s = 0.f;
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    const int ch = tid + c * 1024;
-    if (ch < nchunk) {
-      Ld8<TA>::load(ap + (int64_t)ch * 8, v[c]);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) s += v[c][e];
-    }
-  }
-  const float mean = block_sum(s) / (float)group;
-  float q = 0.f;
-#pragma unroll
-  for (int c = 0; c < NCH; ++c)
-    if (tid + c * 1024 < nchunk) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { const float d = v[c][e] - mean; q += d * d; }
-    }
-  const float rstd = rsqrtf(block_sum(q) / (float)group + eps);
+  const auto [mean, rstd] = adp_slab_stats<TA, NCH>(a + (int64_t)blockIdx.x * group, group, eps, v, sc);
   float s1 = 0.f, s2 = 0.f;
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
     const int ch = tid + c * 1024;
     if (ch < nchunk) {
       float dd[8], ww[8], bb[8];
-      Ld8<T>::load(dp + (int64_t)ch * 8, dd);
-      Ld8<float>::load(w + (int64_t)ch * 8, ww);
-      Ld8<float>::load(b + (int64_t)ch * 8, bb);
+      Vec<T, 8>::load(dp + (int64_t)ch * 8, dd);
+      Vec<float, 8>::load(w + (int64_t)ch * 8, ww);
+      Vec<float, 8>::load(b + (int64_t)ch * 8, bb);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const float nh = (v[c][e] - mean) * rstd;
         v[c][e] = nh;  // keep the normalised value
-        const float g = dd[e] * gelu_erf_grad(nh * ww[e] + bb[e]) * ww[e];
+        const float g = adp_dz(dd[e], nh, ww[e], bb[e], 0) * ww[e];
         s1 += g;
         s2 += g * nh;
       }
     }
   }
-  const float m1 = block_sum(s1) / (float)group, m2 = block_sum(s2) / (float)group;
+  const float m1 = block_sum<16>(s1, sc) / (float)group, m2 = block_sum<16>(s2, sc) / (float)group;
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
     const int ch = tid + c * 1024;
     if (ch < nchunk) {
       float dd[8], ww[8], bb[8], o[8];
-      Ld8<T>::load(dp + (int64_t)ch * 8, dd);
-      Ld8<float>::load(w + (int64_t)ch * 8, ww);
-      Ld8<float>::load(b + (int64_t)ch * 8, bb);
+      Vec<T, 8>::load(dp + (int64_t)ch * 8, dd);
+      Vec<float, 8>::load(w + (int64_t)ch * 8, ww);
+      Vec<float, 8>::load(b + (int64_t)ch * 8, bb);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const float nh = v[c][e];
-        const float g = dd[e] * gelu_erf_grad(nh * ww[e] + bb[e]) * ww[e];
+        const float g = adp_dz(dd[e], nh, ww[e], bb[e], 0) * ww[e];
         o[e] = rstd * (g - m1 - nh * m2);
       }
-      St8<T>::store(op + (int64_t)ch * 8, o);
+      Vec<T, 8>::store(op + (int64_t)ch * 8, o);
     }
   }
   if (tid == 0) { stats[2 * blockIdx.x] = mean; stats[2 * blockIdx.x + 1] = rstd; }
@@ -396,9 +309,8 @@ __global__ __launch_bounds__(256) void adapter_bwd_affine_kernel(const TA* __res
     const float mean = stats[2 * gi], rstd = stats[2 * gi + 1];
     for (int r = 0; r < reps; ++r) {
       const int64_t idx = gi * group + (int64_t)r * affine + e;
-      const float av = ld(a + idx);
-      const float nh = ((gelu_first ? gelu_erf(av) : av) - mean) * rstd;
-      const float dz = ld(dy + idx) * (gelu_first ? 1.0f : gelu_erf_grad(nh * we + be));
+      const float nh = (adp_in(a, idx, gelu_first) - mean) * rstd;
+      const float dz = adp_dz(ld(dy + idx), nh, we, be, gelu_first);
       dw = fmaf(dz, nh, dw);
       db += dz;
     }
@@ -417,7 +329,35 @@ __global__ void adapter_bwd_affine_reduce_kernel(const float* __restrict__ part,
   db[e] = s1;
 }
 
-int affine_slabs(int64_t groups, int affine) {
+// ---- host: one call description, one check, one plan, one launch per direction ------------------------------------
+struct AdpCall {
+  const void* a = nullptr;
+  int a_dtype = DFD_F32;
+  void* out = nullptr;       // forward: y; backward: da
+  const void* dy = nullptr;  // backward
+  int dtype = DFD_F32;       // of y, or of dy and da
+  const float *weight = nullptr, *bias = nullptr;
+  float *dweight = nullptr, *dbias = nullptr;  // backward
+  void* workspace = nullptr;                   // backward: the groups' (mean, rstd), then the affine partial slabs
+  int frames = 0, patches = 0, x = 0;
+  int mode = 0;  // 0: GELU(LN(a)) per row; 1: joint over a frame's (patches, x) slab; 2: LN(GELU(a)) per row
+  float eps = 0.f;
+  bool no_pointers = false;  // the plan hook's call: nothing to check or read but `misaligned`
+  bool misaligned = false;   // no_pointers: what the hook was told
+};
+
+struct AdpPlan {
+  int path = 0;                   // DFD_ADP_* of the forward kernel or the backward's group pass; 0: nothing to launch
+  int64_t grid = 0;               // of that kernel, as computed: adp_check refuses what does not fit a grid dimension
+  unsigned block = 0;
+  int64_t groups = 0;             // normalisation groups: frames (joint) or rows
+  int64_t group = 0;              // elements of one, which is also the affine's extent
+  int slabs = 0, groups_per_slab = 0;  // backward: the affine pass's partial slabs
+};
+
+constexpr int64_t kAdpRegLimit = 1024 * 8 * 7;  // register-resident slab: 7 chunks x 1024 threads x 8 elements
+
+int affine_slabs(int64_t groups, int64_t affine) {
   // enough (element, chunk) threads to cover the chip; at most 512 slabs
   int64_t want = (262144 + affine - 1) / affine;
   if (want > groups) want = groups;
@@ -426,102 +366,154 @@ int affine_slabs(int64_t groups, int affine) {
   return (int)want;
 }
 
+// The vector kernels' 16-byte accesses: a, the output, dy (backward), weight and bias.
+bool adp_misaligned(const AdpCall& c) {
+  if (c.no_pointers) return c.misaligned;
+  return !(dfd_aligned16(c.a) && dfd_aligned16(c.out) && dfd_aligned16(c.dy) && dfd_aligned16(c.weight) && dfd_aligned16(c.bias));
+}
+
+// Which kernel serves a call and with which launch; the table is in include/dfdclip_hooks.h.  Wants positive patches
+// and x; everything is computed in 64 bits, so it may run before adp_check has bounded the extents.
+AdpPlan adp_plan(const AdpCall& c, bool backward) {
+  AdpPlan p;
+  const bool joint = c.mode == 1, vec = !adp_misaligned(c);
+  p.groups = joint ? c.frames : (int64_t)c.frames * c.patches;
+  p.group = joint ? (int64_t)c.patches * c.x : c.x;
+  if (p.groups <= 0) return p;
+  if (joint) {
+    p.path = vec && p.group % 8 == 0 && p.group <= kAdpRegLimit ? DFD_ADP_JOINT_REG : DFD_ADP_JOINT;
+    p.grid = p.groups, p.block = 1024;
+  } else if (vec && c.x == 256) {
+    p.path = DFD_ADP_ROW256, p.grid = (p.groups + 3) / 4, p.block = 256;
+  } else {  // one wave per row: four to a workgroup forward, a workgroup of its own backward
+    p.path = DFD_ADP_ROW, p.grid = backward ? p.groups : (p.groups + 3) / 4, p.block = backward ? 64 : 256;
+  }
+  if (backward) {
+    p.slabs = affine_slabs(p.groups, p.group);
+    p.groups_per_slab = (int)((p.groups + p.slabs - 1) / p.slabs);
+  }
+  return p;
+}
+
+// Every rule of dfd_adapter_norm_gelu and dfd_adapter_norm_gelu_bwd, under the entry point's name.  Forward takes
+// frames == 0 (nothing is launched) and y == a where the two have one dtype; backward needs frames > 0, its workspace,
+// and a da that is neither dy nor a.
+int adp_check(const char* fn, const AdpCall& c, bool backward) {
+  DFD_REQUIRE(c.no_pointers || (c.a && c.out && c.weight && c.bias && (!backward || (c.dy && c.dweight && c.dbias && c.workspace))),
+              "%s: null pointer", fn);
+  DFD_REQUIRE(c.frames >= (backward ? 1 : 0) && c.patches > 0 && c.x > 0, "%s: bad shape", fn);
+  DFD_REQUIRE(c.no_pointers || !backward || (c.out != c.dy && c.out != c.a),
+              "%s: da must not alias dy or a (both are re-read by the affine pass)", fn);
+  DFD_REQUIRE(ok_dtype(c.dtype), "%s: dtype=%d", fn, c.dtype);
+  DFD_REQUIRE(c.a_dtype == c.dtype || c.a_dtype == DFD_F32, "%s: a_dtype=%d must be dtype or f32", fn, c.a_dtype);
+  DFD_REQUIRE(c.no_pointers || backward || c.a_dtype == c.dtype || c.a != c.out, "%s: in place needs one dtype", fn);
+  DFD_REQUIRE(c.mode >= 0 && c.mode <= 2, "%s: mode=%d", fn, c.mode);
+  DFD_REQUIRE((int64_t)c.patches * c.x < (1ll << 31), "%s: patches * x = %lld must be below 2^31", fn, (long long)c.patches * c.x);
+  DFD_REQUIRE(adp_plan(c, backward).grid <= 0x7fffffff, "%s: frames=%d patches=%d: the groups do not fit a grid of 2^31 - 1", fn,
+              c.frames, c.patches);
+  return DFD_OK;
+}
+
+thread_local int g_adp_last_path = 0;
+
+int adp_launch_fwd(const char* fn, const AdpCall& c, const AdpPlan& p, hipStream_t st) {
+  const dim3 grid((unsigned)p.grid), block(p.block);
+  const int slab = (int)p.group, gelu_first = c.mode == 2;
+  with_types<false>(c.a_dtype, c.dtype, [&](auto ta, auto t) {
+    using TA = typename decltype(ta)::type;
+    using T = typename decltype(t)::type;
+    const TA* a = static_cast<const TA*>(c.a);
+    T* y = static_cast<T*>(c.out);
+    if (p.path == DFD_ADP_JOINT_REG)
+      hipLaunchKernelGGL((adapter_nln_reg_kernel<TA, T, 7>), grid, block, 0, st, a, y, c.weight, c.bias, slab, c.eps);
+    else if (p.path == DFD_ADP_JOINT)
+      hipLaunchKernelGGL((adapter_nln_kernel<TA, T>), grid, block, 0, st, a, y, c.weight, c.bias, slab, c.eps);
+    else if (p.path == DFD_ADP_ROW256)
+      hipLaunchKernelGGL((adapter_row256_kernel<TA, T>), grid, block, 0, st, a, y, c.weight, c.bias, p.groups, c.eps, gelu_first);
+    else
+      hipLaunchKernelGGL((adapter_ln_kernel<TA, T>), grid, block, 0, st, a, y, c.weight, c.bias, p.groups, c.x, c.eps, gelu_first);
+  });
+  DFD_CHECK_LAUNCH(fn);
+  return DFD_OK;
+}
+
+// group pass, affine partials, affine reduction: three launches under one launch check
+int adp_launch_bwd(const char* fn, const AdpCall& c, const AdpPlan& p, hipStream_t st) {
+  const dim3 grid((unsigned)p.grid), block(p.block);
+  const int group = (int)p.group, affine = group, gelu_first = c.mode == 2;
+  float* stats = static_cast<float*>(c.workspace);
+  float* part = stats + p.groups * 2;
+  with_types<false>(c.a_dtype, c.dtype, [&](auto ta, auto t) {
+    using TA = typename decltype(ta)::type;
+    using T = typename decltype(t)::type;
+    const TA* a = static_cast<const TA*>(c.a);
+    const T* dy = static_cast<const T*>(c.dy);
+    T* da = static_cast<T*>(c.out);
+    if (p.path == DFD_ADP_ROW256)
+      hipLaunchKernelGGL((adapter_bwd_row256_kernel<TA, T>), grid, block, 0, st, a, dy, da, c.weight, c.bias, stats, p.groups, c.eps,
+                         gelu_first);
+    else if (p.path == DFD_ADP_JOINT_REG)
+      hipLaunchKernelGGL((adapter_bwd_group_reg_kernel<TA, T, 7>), grid, block, 0, st, a, dy, da, c.weight, c.bias, stats, group, c.eps);
+    else
+      hipLaunchKernelGGL((adapter_bwd_group_kernel<TA, T>), grid, block, 0, st, a, dy, da, c.weight, c.bias, stats, group, affine,
+                         c.eps, gelu_first);
+    hipLaunchKernelGGL((adapter_bwd_affine_kernel<TA, T>), dim3((affine + 255) / 256, p.slabs), dim3(256), 0, st, a, dy, c.weight,
+                       c.bias, stats, part, p.groups, group, affine, p.groups_per_slab, gelu_first);
+  });
+  hipLaunchKernelGGL(adapter_bwd_affine_reduce_kernel, dim3((affine + 255) / 256), dim3(256), 0, st, part, c.dweight, c.dbias, affine,
+                     p.slabs);
+  DFD_CHECK_LAUNCH(fn);
+  return DFD_OK;
+}
+
+int adp_run(const char* fn, const AdpCall& c, bool backward, void* stream) {
+  if (int rc = adp_check(fn, c, backward)) return rc;
+  const AdpPlan p = adp_plan(c, backward);
+  if (p.path == 0) return DFD_OK;  // forward with frames == 0
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = backward ? adp_launch_bwd(fn, c, p, st) : adp_launch_fwd(fn, c, p, st)) return rc;
+  g_adp_last_path = p.path;
+  return DFD_OK;
+}
+
 }  // namespace
 
 extern "C" size_t dfd_adapter_norm_gelu_bwd_workspace(int frames, int patches, int x, int joint) {
-  if (frames <= 0 || patches <= 0 || x <= 0) return 0;
-  const bool jt = joint == 1;
-  const int64_t groups = jt ? frames : (int64_t)frames * patches;
-  const int affine = jt ? patches * x : x;
-  return (size_t)groups * 2 * sizeof(float) + (size_t)affine_slabs(groups, affine) * 2 * affine * sizeof(float);
+  if (frames <= 0 || patches <= 0 || x <= 0 || (int64_t)patches * x >= (1ll << 31)) return 0;
+  AdpCall c;
+  c.frames = frames, c.patches = patches, c.x = x, c.mode = joint == 1, c.no_pointers = true;
+  const AdpPlan p = adp_plan(c, true);
+  return (size_t)p.groups * 2 * sizeof(float) + (size_t)p.slabs * 2 * (size_t)p.group * sizeof(float);
 }
 
 extern "C" int dfd_adapter_norm_gelu_bwd(const void* a, int a_dtype, const void* dy, void* da, int dtype, const float* weight,
                                          const float* bias, float* dweight, float* dbias, void* workspace, int frames,
                                          int patches, int x, int joint, float eps, void* stream) {
-  DFD_REQUIRE(a && dy && da && weight && bias && dweight && dbias && workspace, "dfd_adapter_norm_gelu_bwd: null pointer");
-  DFD_REQUIRE(frames > 0 && patches > 0 && x > 0, "dfd_adapter_norm_gelu_bwd: bad shape");
-  DFD_REQUIRE(da != dy && da != a, "dfd_adapter_norm_gelu_bwd: da must not alias dy or a (both are re-read by the affine pass)");
-  DFD_REQUIRE(dtype == DFD_F32 || dtype == DFD_BF16, "dfd_adapter_norm_gelu_bwd: dtype=%d", dtype);
-  DFD_REQUIRE(a_dtype == dtype || a_dtype == DFD_F32, "dfd_adapter_norm_gelu_bwd: a_dtype=%d must be dtype or f32", a_dtype);
-  DFD_REQUIRE(joint >= 0 && joint <= 2, "dfd_adapter_norm_gelu_bwd: mode=%d", joint);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int gelu_first = joint == 2;
-  joint = joint == 1;
-  const int64_t groups = joint ? frames : (int64_t)frames * patches;
-  const int group = joint ? patches * x : x;
-  const int affine = group;
-  float* stats = static_cast<float*>(workspace);
-  float* part = stats + groups * 2;
-  const int slabs = affine_slabs(groups, affine);
-  const int gps = (int)((groups + slabs - 1) / slabs);
-  const int threads = joint ? 1024 : 64;
-  const bool reg_ok = joint && group % 8 == 0 && group <= 1024 * 8 * 7 && dfd_aligned16(a) && dfd_aligned16(dy) &&
-                      dfd_aligned16(da) && dfd_aligned16(weight) && dfd_aligned16(bias);
-  const bool row256 = !joint && group == 256 && dfd_aligned16(a) && dfd_aligned16(dy) && dfd_aligned16(da) &&
-                      dfd_aligned16(weight) && dfd_aligned16(bias);
-#define ADP_LAUNCH(TA, T)                                                                                                 \
-  if (row256)                                                                                                             \
-    hipLaunchKernelGGL((adapter_bwd_row256_kernel<TA, T>), dim3((unsigned)((groups + 3) / 4)), dim3(256), 0, st,             \
-                       static_cast<const TA*>(a), static_cast<const T*>(dy), static_cast<T*>(da), weight, bias, stats,      \
-                       groups, eps, gelu_first);                                                                          \
-  else if (reg_ok)                                                                                                        \
-    hipLaunchKernelGGL((adapter_bwd_group_reg_kernel<TA, T, 7>), dim3((unsigned)groups), dim3(1024), 0, st,                  \
-                       static_cast<const TA*>(a), static_cast<const T*>(dy), static_cast<T*>(da), weight, bias, stats,      \
-                       group, eps);                                                                                       \
-  else                                                                                                                    \
-    hipLaunchKernelGGL((adapter_bwd_group_kernel<TA, T>), dim3((unsigned)groups), dim3(threads), 0, st,                      \
-                       static_cast<const TA*>(a), static_cast<const T*>(dy), static_cast<T*>(da), weight, bias, stats,      \
-                       group, affine, eps, gelu_first);                                                                   \
-  hipLaunchKernelGGL((adapter_bwd_affine_kernel<TA, T>), dim3((affine + 255) / 256, slabs), dim3(256), 0, st,                \
-                     static_cast<const TA*>(a), static_cast<const T*>(dy), weight, bias, stats, part, groups, group, affine, \
-                     gps, gelu_first);
-  if (dtype == DFD_F32) { ADP_LAUNCH(float, float) }
-  else if (a_dtype == DFD_F32) { ADP_LAUNCH(float, bf16_t) }
-  else { ADP_LAUNCH(bf16_t, bf16_t) }
-#undef ADP_LAUNCH
-  hipLaunchKernelGGL(adapter_bwd_affine_reduce_kernel, dim3((affine + 255) / 256), dim3(256), 0, st, part, dweight, dbias, affine, slabs);
-  DFD_CHECK_LAUNCH("dfd_adapter_norm_gelu_bwd");
-  return DFD_OK;
+  AdpCall c;
+  c.a = a, c.a_dtype = a_dtype, c.dy = dy, c.out = da, c.dtype = dtype, c.weight = weight, c.bias = bias;
+  c.dweight = dweight, c.dbias = dbias, c.workspace = workspace;
+  c.frames = frames, c.patches = patches, c.x = x, c.mode = joint, c.eps = eps;
+  return adp_run("dfd_adapter_norm_gelu_bwd", c, true, stream);
 }
 
 extern "C" int dfd_adapter_norm_gelu(const void* a, int a_dtype, void* y, int dtype, const float* weight, const float* bias, int frames,
                                      int patches, int x, int joint, float eps, void* stream) {
-  DFD_REQUIRE(a && y && weight && bias, "dfd_adapter_norm_gelu: null pointer");
-  DFD_REQUIRE(frames >= 0 && patches > 0 && x > 0, "dfd_adapter_norm_gelu: bad shape");
-  DFD_REQUIRE(dtype == DFD_F32 || dtype == DFD_BF16, "dfd_adapter_norm_gelu: dtype=%d", dtype);
-  DFD_REQUIRE(a_dtype == dtype || a_dtype == DFD_F32, "dfd_adapter_norm_gelu: a_dtype=%d must be dtype or f32", a_dtype);
-  DFD_REQUIRE(a_dtype == dtype || a != y, "dfd_adapter_norm_gelu: in place needs one dtype");
-  DFD_REQUIRE(joint >= 0 && joint <= 2, "dfd_adapter_norm_gelu: mode=%d", joint);
-  if (frames == 0) return DFD_OK;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int gelu_first = joint == 2;
-  const int64_t rows = (int64_t)frames * patches;
-  const dim3 grid((unsigned)((rows + 3) / 4));
-  const int slab_all = patches * x;
-  // register-resident slab: 16-byte loads need slab % 8 == 0 and aligned bases; 7 chunks x 1024 threads x 8
-  const bool reg_ok = slab_all % 8 == 0 && slab_all <= 1024 * 8 * 7 && dfd_aligned16(a) && dfd_aligned16(y) &&
-                      dfd_aligned16(weight) && dfd_aligned16(bias);
-  const bool row_ok = dfd_aligned16(a) && dfd_aligned16(y) && dfd_aligned16(weight) && dfd_aligned16(bias);
-#define FWD_LAUNCH(TA, T)                                                                                              \
-  do {                                                                                                                 \
-    if (joint == 1 && reg_ok)                                                                                          \
-      hipLaunchKernelGGL((adapter_nln_reg_kernel<TA, T, 7>), dim3(frames), dim3(1024), 0, st, static_cast<const TA*>(a), \
-                         static_cast<T*>(y), weight, bias, patches * x, eps);                                          \
-    else if (joint == 1)                                                                                               \
-      hipLaunchKernelGGL((adapter_nln_kernel<TA, T>), dim3(frames), dim3(1024), 0, st, static_cast<const TA*>(a),        \
-                         static_cast<T*>(y), weight, bias, patches * x, eps);                                          \
-    else if (joint != 1 && x == 256 && row_ok)                                                                         \
-      hipLaunchKernelGGL((adapter_row256_kernel<TA, T>), grid, dim3(256), 0, st, static_cast<const TA*>(a),              \
-                         static_cast<T*>(y), weight, bias, rows, eps, gelu_first);                                     \
-    else                                                                                                               \
-      hipLaunchKernelGGL((adapter_ln_kernel<TA, T>), grid, dim3(256), 0, st, static_cast<const TA*>(a), static_cast<T*>(y), \
-                         weight, bias, rows, x, eps, gelu_first);                                                      \
-  } while (0)
-  if (dtype == DFD_F32) FWD_LAUNCH(float, float);
-  else if (a_dtype == DFD_F32) FWD_LAUNCH(float, bf16_t);
-  else FWD_LAUNCH(bf16_t, bf16_t);
-#undef FWD_LAUNCH
-  DFD_CHECK_LAUNCH("dfd_adapter_norm_gelu");
-  return DFD_OK;
+  AdpCall c;
+  c.a = a, c.a_dtype = a_dtype, c.out = y, c.dtype = dtype, c.weight = weight, c.bias = bias;
+  c.frames = frames, c.patches = patches, c.x = x, c.mode = joint, c.eps = eps;
+  return adp_run("dfd_adapter_norm_gelu", c, false, stream);
+}
+
+extern "C" int dfd_adapter_norm_gelu_last_path(void) { return g_adp_last_path; }
+
+extern "C" int dfd_adapter_norm_gelu_plan(int frames, int patches, int x, int joint, int a_dtype, int dtype, int misaligned, int backward,
+                                          dfd_adapter_plan_t* out) {
+  const char* fn = backward ? "dfd_adapter_norm_gelu_bwd" : "dfd_adapter_norm_gelu";
+  AdpCall c;
+  c.a_dtype = a_dtype, c.dtype = dtype, c.frames = frames, c.patches = patches, c.x = x, c.mode = joint;
+  c.no_pointers = true, c.misaligned = misaligned != 0;
+  if (adp_check(fn, c, backward != 0) != DFD_OK) return -1;
+  const AdpPlan p = adp_plan(c, backward != 0);
+  if (out) *out = dfd_adapter_plan_t{p.path, (uint32_t)p.grid, p.block, p.slabs, p.groups_per_slab};
+  return p.path;
 }

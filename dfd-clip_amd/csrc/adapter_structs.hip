@@ -8,6 +8,7 @@
 // to a workspace slab, and one wave per channel merges a channel's partials in a fixed order (Chan's parallel update;
 // no float atomics, no E[y²] - E[y]², which cancels at the 2.4 M values of a channel at B16xT30).  The backward's two
 // sums (Σdz, Σdz·ŷ) take the same partial-slab route.  All streaming kernels move 16 bytes per lane per access.
+#include "adapter_common.hpp"
 #include "dropout.hpp"
 #include "gelu.hpp"
 
@@ -16,32 +17,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kIters = 4;                          // 16-byte loads per thread per chunk
 constexpr int kChunk = kThreads * 8 * kIters;      // elements of one frame a statistics block covers
-
-template <typename T> struct V8;
-template <> struct V8<float> {
-  static __device__ __forceinline__ void load(const float* p, float* o) {
-    const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { o[e] = a[e]; o[4 + e] = b[e]; }
-  }
-  static __device__ __forceinline__ void store(float* p, const float* o) {
-    *reinterpret_cast<f32x4*>(p) = f32x4{o[0], o[1], o[2], o[3]};
-    *reinterpret_cast<f32x4*>(p + 4) = f32x4{o[4], o[5], o[6], o[7]};
-  }
-};
-template <> struct V8<bf16_t> {
-  static __device__ __forceinline__ void load(const bf16_t* p, float* o) {
-    const bf16x8 a = *reinterpret_cast<const bf16x8*>(p);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = (float)a[e];
-  }
-  static __device__ __forceinline__ void store(bf16_t* p, const float* o) {
-    bf16x8 r;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) r[e] = (bf16_t)o[e];
-    *reinterpret_cast<bf16x8*>(p) = r;
-  }
-};
 
 // gelu_erf / gelu_erf_grad: gelu.hpp (shared with the GEMM epilogue)
 
@@ -77,7 +52,7 @@ __global__ __launch_bounds__(kThreads) void bn_partial_kernel(const T* __restric
   for (int it = 0; it < kIters; ++it) {
     const int i = c * kChunk + (it * kThreads + (int)threadIdx.x) * 8;
     if (i < slab) {  // slab % 8 == 0: a vector is whole or absent
-      V8<T>::load(base + i, v[it]);
+      Vec<T, 8>::load(base + i, v[it]);
       nv += 8;
 #pragma unroll
       for (int e = 0; e < 8; ++e) s += v[it][e];
@@ -151,7 +126,7 @@ __global__ __launch_bounds__(kThreads) void bn_apply_kernel(const TY* y, const T
     const int t = (int)(frame_div.div(row) % (uint32_t)T_);
     const int64_t e0 = g * 8;
     float v[8];
-    V8<TY>::load(y + e0, v);
+    Vec<TY, 8>::load(y + e0, v);
     if (stats != nullptr) {
       const float mu = stats[t], is = stats[T_ + t], ga = gamma[t], be = beta[t];
 #pragma unroll
@@ -159,12 +134,12 @@ __global__ __launch_bounds__(kThreads) void bn_apply_kernel(const TY* y, const T
     }
     dfd_drop_eight(drop, (uint64_t)e0, v);
     float r[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (residual != nullptr) V8<T>::load(residual + e0, r);
+    if (residual != nullptr) Vec<T, 8>::load(residual + e0, r);
     float p[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (pos != nullptr) V8<float>::load(pos + (int64_t)t * width + col, p);
+    if (pos != nullptr) Vec<float, 8>::load(pos + (int64_t)t * width + col, p);
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = r[e] + v[e] + p[e];
-    V8<T>::store(out + e0, v);
+    Vec<T, 8>::store(out + e0, v);
   }
 }
 
@@ -184,8 +159,8 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_partial_kernel(const T* __res
     if (i < slab) {
       const int64_t e0 = (int64_t)f * slab + i;
       float yv[8], dz[8];
-      V8<T>::load(y + e0, yv);
-      V8<TD>::load(dout + e0, dz);
+      Vec<T, 8>::load(y + e0, yv);
+      Vec<TD, 8>::load(dout + e0, dz);
       dfd_drop_eight(drop, (uint64_t)e0, dz);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
@@ -241,12 +216,12 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_apply_kernel(const T* y, cons
     const float mu = stats[t], is = stats[T_ + t], k = gamma[t] * is;
     const float mb = train ? dbeta[t] * inv_n : 0.f, mg = train ? dgamma[t] * inv_n : 0.f;
     float yv[8], dz[8];
-    V8<T>::load(y + e0, yv);
-    V8<TD>::load(dout + e0, dz);
+    Vec<T, 8>::load(y + e0, yv);
+    Vec<TD, 8>::load(dout + e0, dz);
     dfd_drop_eight(drop, (uint64_t)e0, dz);
 #pragma unroll
     for (int e = 0; e < 8; ++e) yv[e] = k * (dz[e] - mb - ((yv[e] - mu) * is) * mg);
-    V8<T>::store(dy + e0, yv);
+    Vec<T, 8>::store(dy + e0, yv);
   }
 }
 
@@ -258,19 +233,19 @@ __global__ __launch_bounds__(kThreads) void gelu_erf_kernel(const TA* __restrict
   for (int64_t g = (int64_t)blockIdx.x * kThreads + threadIdx.x; g < groups; g += stride) {
     const int64_t e0 = g * 8;
     float v[8];
-    V8<TA>::load(a + e0, v);
+    Vec<TA, 8>::load(a + e0, v);
     if (dh == nullptr) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = gelu_erf(v[e]);
       dfd_drop_eight(drop, (uint64_t)e0, v);
     } else {
       float d[8];
-      V8<TH>::load(dh + e0, d);
+      Vec<TH, 8>::load(dh + e0, d);
       dfd_drop_eight(drop, (uint64_t)e0, d);
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = gelu_erf_grad(v[e]) * d[e];
     }
-    V8<TO>::store(out + e0, v);
+    Vec<TO, 8>::store(out + e0, v);
   }
 }
 
@@ -279,9 +254,25 @@ unsigned stream_grid(int64_t groups) {  // grid-stride: at most 8 blocks of 256 
   return (unsigned)(b < 2048 ? (b > 0 ? b : 1) : 2048);
 }
 
-bool ok_dtype(int d) { return d == DFD_F32 || d == DFD_BF16; }
 
 int chunks_of(int64_t slab) { return (int)((slab + kChunk - 1) / kChunk); }
+
+// What dfd_adapter_bn_apply and dfd_adapter_bn_bwd ask alike of the tensor and of the buffers they move 16 bytes at a time;
+// the backward also needs whole clips (frames > 0, a multiple of T).
+int bn_check(const char* fn, int64_t frames, int patches, int width, int T, bool backward, std::initializer_list<const void*> bufs) {
+  DFD_REQUIRE(T > 0 && frames >= (backward ? 1 : 0) && patches > 0 && width > 0 && (!backward || frames % T == 0) && width % 8 == 0,
+              "%s: bad shape", fn);
+  DFD_REQUIRE(frames * patches * width < (1ll << 31), "%s: tensor of 2^31 elements or more", fn);
+  for (const void* p : bufs) DFD_REQUIRE(dfd_aligned16(p), "%s: buffers must be 16-byte aligned", fn);
+  return DFD_OK;
+}
+
+// What dfd_gelu_erf and dfd_gelu_erf_bwd ask alike: whole groups of 8 and 16-byte aligned buffers.
+int gelu_check(const char* fn, int64_t n, std::initializer_list<const void*> bufs) {
+  DFD_REQUIRE(n >= 0 && n % 8 == 0, "%s: n=%lld must be a multiple of 8", fn, (long long)n);
+  for (const void* p : bufs) DFD_REQUIRE(dfd_aligned16(p), "%s: buffers must be 16-byte aligned", fn);
+  return DFD_OK;
+}
 
 }  // namespace
 
@@ -323,43 +314,36 @@ extern "C" int dfd_adapter_bn_stats(const void* y, int dtype, float* stats, floa
 extern "C" int dfd_adapter_bn_apply(const void* y, int y_dtype, const void* residual, void* out, int dtype, const float* stats,
                                     const float* gamma, const float* beta, const float* pos, const dfd_dropout_t* drop,
                                     int64_t frames, int patches, int width, int T, void* stream) {
-  DFD_REQUIRE(y && out, "dfd_adapter_bn_apply: null pointer");
-  DFD_REQUIRE(!stats || (gamma && beta), "dfd_adapter_bn_apply: stats need gamma and beta");
-  DFD_REQUIRE(ok_dtype(y_dtype) && ok_dtype(dtype), "dfd_adapter_bn_apply: dtypes %d / %d", y_dtype, dtype);
-  DFD_REQUIRE(T > 0 && frames >= 0 && patches > 0 && width > 0 && width % 8 == 0, "dfd_adapter_bn_apply: bad shape");
-  DFD_REQUIRE(frames * patches * width < (1ll << 31), "dfd_adapter_bn_apply: tensor of 2^31 elements or more");
-  DFD_REQUIRE(dfd_aligned16(y) && dfd_aligned16(out) && dfd_aligned16(residual) && dfd_aligned16(pos),
-              "dfd_adapter_bn_apply: buffers must be 16-byte aligned");
-  DFD_REQUIRE(y != out || y_dtype == dtype, "dfd_adapter_bn_apply: in place on y needs one dtype");
-  DFD_REQUIRE(!drop || (drop->p >= 0.f && drop->p < 1.f && (drop->p == 0.f || drop->rng_state)), "dfd_adapter_bn_apply: bad dropout");
+  const char* fn = "dfd_adapter_bn_apply";
+  DFD_REQUIRE(y && out, "%s: null pointer", fn);
+  DFD_REQUIRE(!stats || (gamma && beta), "%s: stats need gamma and beta", fn);
+  DFD_REQUIRE(ok_dtype(y_dtype) && ok_dtype(dtype), "%s: dtypes %d / %d", fn, y_dtype, dtype);
+  if (int rc = bn_check(fn, frames, patches, width, T, false, {y, out, residual, pos})) return rc;
+  DFD_REQUIRE(y != out || y_dtype == dtype, "%s: in place on y needs one dtype", fn);
+  if (int rc = check_drop(fn, drop)) return rc;
   if (frames == 0) return DFD_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int64_t groups = frames * patches * width / 8;
   const FastDiv rd = FastDiv::make((uint32_t)(width / 8)), fd = FastDiv::make((uint32_t)patches);
   const DfdDrop d = dfd_make_drop(drop);
-#define BN_APPLY(TY, T_)                                                                                                  \
-  hipLaunchKernelGGL((bn_apply_kernel<TY, T_>), dim3(stream_grid(groups)), dim3(kThreads), 0, st, static_cast<const TY*>(y), \
-                     static_cast<const T_*>(residual), static_cast<T_*>(out), stats, gamma, beta, pos, groups, rd, fd, width, T, d)
-  if (y_dtype == DFD_F32 && dtype == DFD_F32) BN_APPLY(float, float);
-  else if (y_dtype == DFD_F32) BN_APPLY(float, bf16_t);
-  else if (dtype == DFD_F32) BN_APPLY(bf16_t, float);
-  else BN_APPLY(bf16_t, bf16_t);
-#undef BN_APPLY
-  DFD_CHECK_LAUNCH("dfd_adapter_bn_apply");
+  with_types(y_dtype, dtype, [&](auto ty, auto t) {
+    using TY = typename decltype(ty)::type;
+    using T_ = typename decltype(t)::type;
+    hipLaunchKernelGGL((bn_apply_kernel<TY, T_>), dim3(stream_grid(groups)), dim3(kThreads), 0, st, static_cast<const TY*>(y),
+                       static_cast<const T_*>(residual), static_cast<T_*>(out), stats, gamma, beta, pos, groups, rd, fd, width, T, d);
+  });
+  DFD_CHECK_LAUNCH(fn);
   return DFD_OK;
 }
 
 extern "C" int dfd_adapter_bn_bwd(const void* y, const void* dout, int dout_dtype, void* dy, int dtype, const float* stats,
                                   const float* gamma, float* dgamma, float* dbeta, const dfd_dropout_t* drop, void* workspace,
                                   int64_t frames, int patches, int width, int T, int train, void* stream) {
-  DFD_REQUIRE(y && dout && dy && stats && gamma && dgamma && dbeta && workspace, "dfd_adapter_bn_bwd: null pointer");
-  DFD_REQUIRE(ok_dtype(dtype) && (dout_dtype == dtype || dout_dtype == DFD_F32), "dfd_adapter_bn_bwd: dtypes %d / %d", dtype,
-              dout_dtype);
-  DFD_REQUIRE(T > 0 && frames > 0 && patches > 0 && width > 0 && frames % T == 0 && width % 8 == 0, "dfd_adapter_bn_bwd: bad shape");
-  DFD_REQUIRE(frames * patches * width < (1ll << 31), "dfd_adapter_bn_bwd: tensor of 2^31 elements or more");
-  DFD_REQUIRE(dfd_aligned16(y) && dfd_aligned16(dout) && dfd_aligned16(dy) && dfd_aligned16(workspace),
-              "dfd_adapter_bn_bwd: buffers must be 16-byte aligned");
-  DFD_REQUIRE(!drop || (drop->p >= 0.f && drop->p < 1.f && (drop->p == 0.f || drop->rng_state)), "dfd_adapter_bn_bwd: bad dropout");
+  const char* fn = "dfd_adapter_bn_bwd";
+  DFD_REQUIRE(y && dout && dy && stats && gamma && dgamma && dbeta && workspace, "%s: null pointer", fn);
+  DFD_REQUIRE(ok_dtype(dtype) && (dout_dtype == dtype || dout_dtype == DFD_F32), "%s: dtypes %d / %d", fn, dtype, dout_dtype);
+  if (int rc = bn_check(fn, frames, patches, width, T, true, {y, dout, dy, workspace})) return rc;
+  if (int rc = check_drop(fn, drop)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int slab = patches * width, chunks = chunks_of(slab), clips = (int)(frames / T);
   const int64_t groups = frames * slab / 8;
@@ -367,65 +351,60 @@ extern "C" int dfd_adapter_bn_bwd(const void* y, const void* dout, int dout_dtyp
   const FastDiv fd = FastDiv::make((uint32_t)(slab / 8));
   const float inv_n = 1.0f / ((float)clips * (float)slab);
   const DfdDrop d = dfd_make_drop(drop);
-#define BN_BWD(T_, TD)                                                                                                       \
-  hipLaunchKernelGGL((bn_bwd_partial_kernel<T_, TD>), dim3((unsigned)(frames * chunks)), dim3(kThreads), 0, st,               \
-                     static_cast<const T_*>(y), static_cast<const TD*>(dout), stats, part, slab, chunks, T, d);              \
-  hipLaunchKernelGGL(bn_bwd_merge_kernel, dim3(T), dim3(64), 0, st, part, dgamma, dbeta, clips, T, chunks);                   \
-  hipLaunchKernelGGL((bn_bwd_apply_kernel<T_, TD>), dim3(stream_grid(groups)), dim3(kThreads), 0, st, static_cast<const T_*>(y), \
-                     static_cast<const TD*>(dout), static_cast<T_*>(dy), stats, gamma, dgamma, dbeta, groups, fd, T, inv_n, train, d)
-  if (dtype == DFD_F32) { BN_BWD(float, float); }
-  else if (dout_dtype == DFD_F32) { BN_BWD(bf16_t, float); }
-  else { BN_BWD(bf16_t, bf16_t); }
-#undef BN_BWD
-  DFD_CHECK_LAUNCH("dfd_adapter_bn_bwd");
+  with_types<false>(dout_dtype, dtype, [&](auto td, auto t) {  // dout is in dtype or f32
+    using TD = typename decltype(td)::type;
+    using T_ = typename decltype(t)::type;
+    hipLaunchKernelGGL((bn_bwd_partial_kernel<T_, TD>), dim3((unsigned)(frames * chunks)), dim3(kThreads), 0, st,
+                       static_cast<const T_*>(y), static_cast<const TD*>(dout), stats, part, slab, chunks, T, d);
+    hipLaunchKernelGGL(bn_bwd_merge_kernel, dim3(T), dim3(64), 0, st, part, dgamma, dbeta, clips, T, chunks);
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<T_, TD>), dim3(stream_grid(groups)), dim3(kThreads), 0, st, static_cast<const T_*>(y),
+                       static_cast<const TD*>(dout), static_cast<T_*>(dy), stats, gamma, dgamma, dbeta, groups, fd, T, inv_n, train, d);
+  });
+  DFD_CHECK_LAUNCH(fn);
   return DFD_OK;
 }
 
 extern "C" int dfd_gelu_erf(const void* a, int a_dtype, void* out, int out_dtype, int64_t n, const dfd_dropout_t* drop,
                             void* stream) {
-  DFD_REQUIRE(a && out, "dfd_gelu_erf: null pointer");
-  DFD_REQUIRE(ok_dtype(a_dtype) && ok_dtype(out_dtype), "dfd_gelu_erf: dtypes %d / %d", a_dtype, out_dtype);
-  DFD_REQUIRE(n >= 0 && n % 8 == 0, "dfd_gelu_erf: n=%lld must be a multiple of 8", (long long)n);
-  DFD_REQUIRE(dfd_aligned16(a) && dfd_aligned16(out), "dfd_gelu_erf: buffers must be 16-byte aligned");
-  DFD_REQUIRE(a != out || a_dtype == out_dtype, "dfd_gelu_erf: in place needs one dtype");
-  DFD_REQUIRE(!drop || (drop->p >= 0.f && drop->p < 1.f && (drop->p == 0.f || drop->rng_state)), "dfd_gelu_erf: bad dropout");
+  const char* fn = "dfd_gelu_erf";
+  DFD_REQUIRE(a && out, "%s: null pointer", fn);
+  DFD_REQUIRE(ok_dtype(a_dtype) && ok_dtype(out_dtype), "%s: dtypes %d / %d", fn, a_dtype, out_dtype);
+  if (int rc = gelu_check(fn, n, {a, out})) return rc;
+  DFD_REQUIRE(a != out || a_dtype == out_dtype, "%s: in place needs one dtype", fn);
+  if (int rc = check_drop(fn, drop)) return rc;
   if (n == 0) return DFD_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const DfdDrop d = dfd_make_drop(drop);
   const int64_t groups = n / 8;
-#define GELU_FWD(TA, TO)                                                                                                   \
-  hipLaunchKernelGGL((gelu_erf_kernel<TA, TA, TO>), dim3(stream_grid(groups)), dim3(kThreads), 0, st,                       \
-                     static_cast<const TA*>(a), static_cast<const TA*>(nullptr), static_cast<TO*>(out), groups, d)
-  if (a_dtype == DFD_F32 && out_dtype == DFD_F32) GELU_FWD(float, float);
-  else if (a_dtype == DFD_F32) GELU_FWD(float, bf16_t);
-  else if (out_dtype == DFD_F32) GELU_FWD(bf16_t, float);
-  else GELU_FWD(bf16_t, bf16_t);
-#undef GELU_FWD
-  DFD_CHECK_LAUNCH("dfd_gelu_erf");
+  with_types(a_dtype, out_dtype, [&](auto ta, auto to) {
+    using TA = typename decltype(ta)::type;
+    using TO = typename decltype(to)::type;
+    hipLaunchKernelGGL((gelu_erf_kernel<TA, TA, TO>), dim3(stream_grid(groups)), dim3(kThreads), 0, st, static_cast<const TA*>(a),
+                       static_cast<const TA*>(nullptr), static_cast<TO*>(out), groups, d);
+  });
+  DFD_CHECK_LAUNCH(fn);
   return DFD_OK;
 }
 
 extern "C" int dfd_gelu_erf_bwd(const void* a, int a_dtype, const void* dh, int dh_dtype, void* da, int da_dtype, int64_t n,
                                 const dfd_dropout_t* drop, void* stream) {
-  DFD_REQUIRE(a && dh && da, "dfd_gelu_erf_bwd: null pointer");
+  const char* fn = "dfd_gelu_erf_bwd";
+  DFD_REQUIRE(a && dh && da, "%s: null pointer", fn);
   DFD_REQUIRE(ok_dtype(a_dtype) && ok_dtype(dh_dtype) && ok_dtype(da_dtype) && dh_dtype == da_dtype,
-              "dfd_gelu_erf_bwd: dtypes %d / %d / %d (dh and da must agree)", a_dtype, dh_dtype, da_dtype);
-  DFD_REQUIRE(n >= 0 && n % 8 == 0, "dfd_gelu_erf_bwd: n=%lld must be a multiple of 8", (long long)n);
-  DFD_REQUIRE(dfd_aligned16(a) && dfd_aligned16(dh) && dfd_aligned16(da), "dfd_gelu_erf_bwd: buffers must be 16-byte aligned");
-  DFD_REQUIRE(da != a || a_dtype == da_dtype, "dfd_gelu_erf_bwd: in place on a needs one dtype");
-  DFD_REQUIRE(!drop || (drop->p >= 0.f && drop->p < 1.f && (drop->p == 0.f || drop->rng_state)), "dfd_gelu_erf_bwd: bad dropout");
+              "%s: dtypes %d / %d / %d (dh and da must agree)", fn, a_dtype, dh_dtype, da_dtype);
+  if (int rc = gelu_check(fn, n, {a, dh, da})) return rc;
+  DFD_REQUIRE(da != a || a_dtype == da_dtype, "%s: in place on a needs one dtype", fn);
+  if (int rc = check_drop(fn, drop)) return rc;
   if (n == 0) return DFD_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const DfdDrop d = dfd_make_drop(drop);
   const int64_t groups = n / 8;
-#define GELU_BWD(TA, T_)                                                                                                   \
-  hipLaunchKernelGGL((gelu_erf_kernel<TA, T_, T_>), dim3(stream_grid(groups)), dim3(kThreads), 0, st,                       \
-                     static_cast<const TA*>(a), static_cast<const T_*>(dh), static_cast<T_*>(da), groups, d)
-  if (a_dtype == DFD_F32 && da_dtype == DFD_F32) GELU_BWD(float, float);
-  else if (a_dtype == DFD_F32) GELU_BWD(float, bf16_t);
-  else if (da_dtype == DFD_F32) GELU_BWD(bf16_t, float);
-  else GELU_BWD(bf16_t, bf16_t);
-#undef GELU_BWD
-  DFD_CHECK_LAUNCH("dfd_gelu_erf_bwd");
+  with_types(a_dtype, da_dtype, [&](auto ta, auto t) {
+    using TA = typename decltype(ta)::type;
+    using T_ = typename decltype(t)::type;
+    hipLaunchKernelGGL((gelu_erf_kernel<TA, T_, T_>), dim3(stream_grid(groups)), dim3(kThreads), 0, st, static_cast<const TA*>(a),
+                       static_cast<const T_*>(dh), static_cast<T_*>(da), groups, d);
+  });
+  DFD_CHECK_LAUNCH(fn);
   return DFD_OK;
 }

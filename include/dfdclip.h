@@ -283,13 +283,15 @@ int dfd_dropout(const void* in, int in_dtype, void* out, int out_dtype, int64_t 
  * ("768-x-768" / "legacy-768-x-768", models.py:795-821): y = LayerNorm(GELU(a)) per row of x — the same two
  * stages in the other order.  `a` is in a_dtype = dtype, or f32 with a bf16 y (the GELU-first structs keep
  * the projection output in f32: LayerNorm after the non-linearity amplifies its rounding).  y may alias a
- * when the dtypes agree.  The backward takes the same mode and a_dtype. */
+ * when the dtypes agree.  The backward takes the same mode and a_dtype.  Both refuse, on the host, a
+ * patches * x of 2^31 or more and a frame or row count whose workgroups do not fit a grid of 2^31 - 1. */
 int dfd_adapter_norm_gelu(const void* a, int a_dtype, void* y, int dtype, const float* weight, const float* bias, int frames,
                           int patches, int x, int joint, float eps, void* stream);
 
 /* Backward of dfd_adapter_norm_gelu: a = the forward's input, dy = dL/dy; writes da = dL/da (same dtype;
- * must NOT alias dy: the affine pass re-reads dy) and the affine gradients dweight / dbias (shapes of weight / bias), summed over frames in
- * a fixed order.  workspace >= dfd_adapter_norm_gelu_bwd_workspace(...) bytes. */
+ * must alias NEITHER dy NOR a: the affine pass re-reads both, and a call with da == dy or da == a is refused) and the
+ * affine gradients dweight / dbias (shapes of weight / bias), summed over frames in a fixed order.  frames > 0.
+ * workspace >= dfd_adapter_norm_gelu_bwd_workspace(...) bytes (0 for a shape the entry point refuses). */
 size_t dfd_adapter_norm_gelu_bwd_workspace(int frames, int patches, int x, int joint);
 int dfd_adapter_norm_gelu_bwd(const void* a, int a_dtype, const void* dy, void* da, int dtype, const float* weight, const float* bias,
                               float* dweight, float* dbias, void* workspace, int frames, int patches, int x, int joint,

@@ -136,6 +136,36 @@ int64_t dfd_gemm_pair_launches(void);
  * dfd_gemm_last_path is to dfd_gemm. */
 int dfd_gemm_at_b_last_path(void);
 
+/* The kernels behind dfd_adapter_norm_gelu and the group pass of dfd_adapter_norm_gelu_bwd, and the rule that picks one
+ * (adp_plan in csrc/adapter.hip is the only code that knows it).  groups = frames (mode 1) or frames * patches (modes 0
+ * and 2); group = patches * x (mode 1) or x; "aligned": a, the output, dy (backward), weight and bias at 16 bytes.
+ *   mode 1, aligned, group % 8 == 0, group <= 57,344 (7 chunks x 1024 threads x 8) -> JOINT_REG: grid groups, block 1024
+ *   mode 1 otherwise                                                               -> JOINT:     grid groups, block 1024
+ *   modes 0 and 2, aligned, x == 256                              -> ROW256: grid ceil(groups / 4), block 256
+ *   modes 0 and 2 otherwise                                       -> ROW: forward grid ceil(groups / 4), block 256;
+ *                                                                         backward grid groups, block 64
+ * Backward then adds the affine gradients in slabs = min(ceil(262,144 / group), groups, 512) partial slabs of
+ * groups_per_slab = ceil(groups / slabs) groups each (slabs past the last group add zeros) and one reduction.
+ * A call whose patches * x reaches 2^31, or whose grid exceeds 2^31 - 1, is refused. */
+enum { DFD_ADP_ROW256 = 1,    /* one wave per 256-wide row, four elements per lane */
+       DFD_ADP_JOINT_REG = 2, /* one workgroup per frame, the slab held in registers */
+       DFD_ADP_JOINT = 3,     /* one workgroup per frame, the slab read once per pass */
+       DFD_ADP_ROW = 4        /* the strided row kernels, any x, any alignment */ };
+typedef struct {
+  int32_t path;                   /* DFD_ADP_*; 0 = forward with frames == 0: nothing is launched */
+  uint32_t grid, block;           /* of the forward kernel, or of the backward's group pass */
+  int32_t slabs, groups_per_slab; /* backward: the affine pass; forward: 0 */
+} dfd_adapter_plan_t;
+
+/* The path (DFD_ADP_*) of this thread's last successful dfd_adapter_norm_gelu or dfd_adapter_norm_gelu_bwd that launched
+ * a kernel; 0 = no call yet. */
+int dfd_adapter_norm_gelu_last_path(void);
+/* What dfd_adapter_norm_gelu (backward == 0) or dfd_adapter_norm_gelu_bwd would do with this shape: returns the path and
+ * fills *out (may be NULL), or returns -1 with dfd_last_error() in the words of that entry point.  misaligned != 0: one
+ * of the pointers named above is not 16-byte aligned.  No pointer and no device is involved. */
+int dfd_adapter_norm_gelu_plan(int frames, int patches, int x, int joint, int a_dtype, int dtype, int misaligned, int backward,
+                               dfd_adapter_plan_t* out);
+
 /* The cache policy of the kernels that touch every byte once.  One bit per family; a set bit makes that family's loads
  * and stores of its read-once (write-once) stream non-temporal, so that they do not evict what the persistent GEMMs of
  * another stream keep in L2.  Results are bit-identical either way (tests/test_hip_stream_policy.py).  Process-wide

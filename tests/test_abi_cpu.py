@@ -161,6 +161,125 @@ def test_layernorm_entry_points_refuse_the_same_arguments(lib):
         assert call(name, cols=2052, ldx=2052, ldy=2052, ldy8=2052) == 0, (name, lib.dfd_last_error())
 
 
+def test_adapter_norm_gelu_plan_table(lib):
+    """The selection table of include/dfdclip_hooks.h (adp_plan in csrc/adapter.hip), through dfd_adapter_norm_gelu_plan, for
+    both directions, every mode, aligned and misaligned bases: path, grid and block of the forward kernel or the backward's
+    group pass, and the backward's affine slabs.  The numbers are written out by hand.  No device is touched."""
+    c = capi
+    REG, JOINT, R256, ROW = c.ADP_JOINT_REG, c.ADP_JOINT, c.ADP_ROW256, c.ADP_ROW
+    F32, BF16 = torch.float32, torch.bfloat16
+    table = {
+        # (frames, patches, x): joint (aligned path, frames, slabs, groups per slab),
+        #                       rows (aligned path, workgroups of four rows, rows, slabs, groups per slab)
+        (5, 196, 256): ((REG, 5, 5, 1), (R256, 245, 980, 512, 2)),     # slab 50,176: 6 slabs wanted, 5 frames
+        (3, 196, 256): ((REG, 3, 3, 1), (R256, 147, 588, 512, 2)),     # 588 rows in 512 slabs of 2: 294..511 stay empty
+        (1, 224, 256): ((REG, 1, 1, 1), (R256, 56, 224, 224, 1)),      # slab 57,344: exactly the register limit
+        (1, 225, 256): ((JOINT, 1, 1, 1), (R256, 57, 225, 225, 1)),    # one row past it
+        (2, 7, 5): ((JOINT, 2, 2, 1), (ROW, 4, 14, 14, 1)),            # slab 35: not a multiple of 8
+        (3, 49, 64): ((REG, 3, 3, 1), (ROW, 37, 147, 147, 1)),
+        (2, 7, 40): ((REG, 2, 2, 1), (ROW, 4, 14, 14, 1)),
+        (2, 3, 1024): ((REG, 2, 2, 1), (ROW, 2, 6, 6, 1)),
+    }
+
+    def plan(shape, mode, mis, bwd, adt=BF16, dt=BF16):
+        p = c.adapter_norm_gelu_plan(*shape, mode, adt, dt, misaligned=mis, backward=bwd)
+        return p.path, p.grid, p.block, p.slabs, p.groups_per_slab
+
+    for shape, (jt, rw) in table.items():
+        for adt, dt in ((F32, F32), (F32, BF16), (BF16, BF16)):
+            for mis in (False, True):
+                path = JOINT if mis else jt[0]
+                assert plan(shape, 1, mis, False, adt, dt) == (path, jt[1], 1024, 0, 0), (shape, mis)
+                assert plan(shape, 1, mis, True, adt, dt) == (path, jt[1], 1024, jt[2], jt[3]), (shape, mis)
+                for mode in (0, 2):
+                    if rw[0] == R256 and not mis:
+                        fwd, bwd = (R256, rw[1], 256), (R256, rw[1], 256)
+                    else:  # forward: four rows to a workgroup of 256; backward: a workgroup of 64 per row
+                        fwd, bwd = (ROW, rw[1], 256), (ROW, rw[2], 64)
+                    assert plan(shape, mode, mis, False, adt, dt) == fwd + (0, 0), (shape, mode, mis)
+                    assert plan(shape, mode, mis, True, adt, dt) == bwd + (rw[3], rw[4]), (shape, mode, mis)
+    # forward with no frames launches nothing; the backward refuses it, in its own words
+    assert plan((0, 196, 256), 1, False, False) == (0, 0, 0, 0, 0)
+    with pytest.raises(c.DfdError, match="dfd_adapter_norm_gelu_bwd: bad shape"):
+        plan((0, 196, 256), 1, False, True)
+    with pytest.raises(c.DfdError, match="dfd_adapter_norm_gelu: mode=3"):
+        plan((1, 196, 256), 3, False, False)
+
+
+def test_adapter_entry_points_refuse_the_same_arguments(lib):
+    """dfd_adapter_norm_gelu and dfd_adapter_norm_gelu_bwd share one argument check (csrc/adapter.hip adp_check): each refuses
+    every bad argument of the table that applies to it on the host, under its own name and with the rule's key phrase,
+    before any launch; the forward accepts the valid call with frames = 0.  A second table holds the dropout-descriptor
+    rule (csrc/adapter_common.hpp check_drop) of the adapter_structs.hip entry points that take a descriptor.  Fake
+    aligned addresses; no pointer is dereferenced."""
+    import ctypes
+    A, Y, DY, W, B, DW, DB, WS = ((i + 1) << 12 for i in range(8))
+    F32, BF16 = capi.F32, capi.BF16
+    fwd, bwd = "dfd_adapter_norm_gelu", "dfd_adapter_norm_gelu_bwd"
+    both = (fwd, bwd)
+
+    def call(name, a=A, adt=BF16, out=Y, dy=DY, dt=BF16, w=W, ws=WS, frames=2, patches=7, x=40, mode=1):
+        if name == fwd:
+            return lib.dfd_adapter_norm_gelu(a, adt, out, dt, w, B, frames, patches, x, mode, 1e-5, None)
+        return lib.dfd_adapter_norm_gelu_bwd(a, adt, dy, out, dt, w, B, DW, DB, ws, frames, patches, x, mode, 1e-5, None)
+
+    bad = [  # (what, arguments, key phrase, the entry points it applies to)
+        ("null a", dict(a=None), "null pointer", both),
+        ("null weight", dict(w=None), "null pointer", both),
+        ("null output", dict(out=None), "null pointer", both),
+        ("null dy", dict(dy=None), "null pointer", (bwd,)),
+        ("null workspace", dict(ws=None), "null pointer", (bwd,)),
+        ("patches = 0", dict(patches=0), "bad shape", both),
+        ("x = -1", dict(x=-1), "bad shape", both),
+        ("frames = -1", dict(frames=-1), "bad shape", both),
+        ("frames = 0", dict(frames=0), "bad shape", (bwd,)),
+        ("dtype = 7", dict(dt=7, adt=7), "dtype=7", both),
+        ("a_dtype = 7", dict(adt=7), "a_dtype=7", both),
+        ("bf16 a beside f32", dict(adt=BF16, dt=F32), "must be dtype or f32", both),
+        ("mode = 3", dict(mode=3), "mode=3", both),
+        ("mode = -1", dict(mode=-1), "mode=-1", both),
+        ("patches * x = 2^31", dict(patches=65536, x=32768), "below 2^31", both),
+        ("patches * x = 2^31, per row", dict(patches=65536, x=32768, mode=0), "below 2^31", both),
+        ("2^35 rows", dict(frames=2 ** 31 - 1, patches=16, x=8, mode=0), "fit a grid", both),
+        ("2^35 rows, GELU first", dict(frames=2 ** 31 - 1, patches=16, x=8, mode=2), "fit a grid", both),
+        ("2^34 rows of 256", dict(frames=2 ** 30, patches=16, x=256, mode=0), "fit a grid", both),
+        ("2^32 rows, one workgroup each", dict(frames=2 ** 30, patches=4, x=8, mode=0), "fit a grid", (bwd,)),
+        ("in place across dtypes", dict(out=A, adt=F32), "in place needs one dtype", (fwd,)),
+        ("da is dy", dict(out=DY), "must not alias", (bwd,)),
+        ("da is a", dict(out=A), "must not alias", (bwd,)),
+    ]
+    for name in both:
+        for what, kw, phrase, applies in bad:
+            if name not in applies:
+                continue
+            assert call(name, **kw) == -1, f"{name}: {what} was accepted"
+            err = lib.dfd_last_error()
+            assert err.startswith(name.encode() + b":") and phrase.encode() in err, (name, what, err)
+    # what the forward accepts without a launch: no frames, in any mode, in place in one dtype, from any alignment
+    for mode in (0, 1, 2):
+        assert call(fwd, frames=0, mode=mode) == 0, lib.dfd_last_error()
+    assert call(fwd, frames=0, out=A) == 0 and call(fwd, frames=0, a=A + 2, out=Y + 2) == 0, lib.dfd_last_error()
+    assert call(fwd, frames=0, adt=F32) == 0 and call(fwd, frames=0, adt=F32, dt=F32, out=A) == 0, lib.dfd_last_error()
+
+    def with_drop(name, drop, n=16):  # valid but for the descriptor; frames = 2, patches = 1, width = 8, T = 1
+        d = ctypes.byref(drop) if drop is not None else None
+        return {
+            "dfd_adapter_bn_apply": lambda: lib.dfd_adapter_bn_apply(A, BF16, None, Y, BF16, None, None, None, None, d, n // 8, 1, 8, 1, None),
+            "dfd_adapter_bn_bwd": lambda: lib.dfd_adapter_bn_bwd(A, DY, BF16, Y, BF16, W, B, DW, DB, d, WS, n // 8, 1, 8, 1, 1, None),
+            "dfd_gelu_erf": lambda: lib.dfd_gelu_erf(A, BF16, Y, BF16, n, d, None),
+            "dfd_gelu_erf_bwd": lambda: lib.dfd_gelu_erf_bwd(A, BF16, DY, BF16, Y, BF16, n, d, None),
+        }[name]()
+
+    bad_drops = {"p = -0.1": capi.DropoutDesc(WS, 3, -0.1), "p = 1": capi.DropoutDesc(WS, 3, 1.0), "p = 0.5 without a state": capi.DropoutDesc(None, 3, 0.5)}
+    for name in ("dfd_adapter_bn_apply", "dfd_adapter_bn_bwd", "dfd_gelu_erf", "dfd_gelu_erf_bwd"):
+        for what, drop in bad_drops.items():
+            assert with_drop(name, drop) == -1, f"{name}: {what} was accepted"
+            assert lib.dfd_last_error() == name.encode() + b": bad dropout", (name, what, lib.dfd_last_error())
+        if name != "dfd_adapter_bn_bwd":  # the three that take an empty tensor: p = 0 needs no state, p > 0 has one
+            assert with_drop(name, capi.DropoutDesc(None, 3, 0.0), n=0) == 0, (name, lib.dfd_last_error())
+            assert with_drop(name, capi.DropoutDesc(WS, 3, 0.5), n=0) == 0 and with_drop(name, None, n=0) == 0, (name, lib.dfd_last_error())
+
+
 def test_gemm_at_b_refuses_rows_the_fallback_cannot_launch(lib):
     """The transpose + general-kernel path of dfd_gemm_at_b puts one block of 32 rows on grid.y: more than 65535 blocks
     are refused on the host, under the function's name, before any launch.  No pointer is dereferenced and nothing is

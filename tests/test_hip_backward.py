@@ -272,37 +272,67 @@ def test_gemm_at_b(capi, R, Ma, Nb, dtype):
     assert torch.equal(c, c2)
 
 
+# (frames, P, x) -> the kernel dfd_adapter_norm_gelu_last_path() must name after the forward and after the backward, as
+# (joint, per row); any of the shapes on views offset by one element: ("JOINT", "ROW"), the kernels without 16-byte accesses
+ADAPTER_NORM_GELU_PATHS = {
+    (5, 196, 256): ("JOINT_REG", "ROW256"),
+    (2, 256, 256): ("JOINT", "ROW256"),
+    (3, 49, 64): ("JOINT_REG", "ROW"),
+    (2, 7, 40): ("JOINT_REG", "ROW"),
+    (1, 224, 256): ("JOINT_REG", "ROW256"),
+    (1, 225, 256): ("JOINT", "ROW256"),
+    (2, 49, 64): ("JOINT_REG", "ROW"),
+}
+
+
 @pytest.mark.parametrize("joint", [True, False])
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, "f32a_bf16"], ids=["f32", "bf16", "f32a_bf16"])
-@pytest.mark.parametrize("frames,P,x", [(5, 196, 256), (2, 256, 256), (3, 49, 64), (2, 7, 40)])
+@pytest.mark.parametrize("frames,P,x", list(ADAPTER_NORM_GELU_PATHS))
 def test_adapter_norm_gelu_backward(capi, frames, P, x, joint, dtype):
     """Adapter middle stage, forward and backward, for the three modes: 0 GELU(LN_row), 1 GELU(LN_joint), 2 LN_row(GELU).
     (5, 196, 256) is the shipped width: the register-resident joint kernels (7th chunk partly filled) and the
     one-wave-per-row kernels; (2, 256, 256) has a slab of 65,536 > 1024 * 8 * 7, the generic joint kernels; (3, 49, 64) a
-    single partial register chunk and the generic row kernels with 64-thread groups; (2, 7, 40) rows narrower than a wave.
+    single partial register chunk and the generic row kernels with 64-thread groups; (2, 7, 40) rows narrower than a wave;
+    (1, 224, 256) is the last slab on the register path (exactly 1024 * 8 * 7) and (1, 225, 256) the first past it.
+    (2, 49, 64) runs twice: as it is, and on views of a, y, dy and da offset by one element, where no base is 16-byte
+    aligned and the generic kernels serve both the joint and the row modes.  After every forward and every backward the
+    library must name the kernel of ADAPTER_NORM_GELU_PATHS.
     "f32a_bf16": `a` stays in f32 beside bf16 y / dy / da, as the training path keeps it for the GELU-first structs."""
     mixed = isinstance(dtype, str)
     a_dtype, dtype = (torch.float32, torch.bfloat16) if mixed else (dtype, dtype)
-    for mode in ((1,) if joint else (0, 2)):
-        a = rnd(frames, P, x, seed=50, scale=1.5).to(a_dtype).float().requires_grad_(True)
-        shape = (P, x) if joint else (x,)
-        w = (1 + 0.1 * rnd(*shape, seed=51)).requires_grad_(True)
-        b = (0.1 * rnd(*shape, seed=52)).requires_grad_(True)
-        dy = rnd(frames, P, x, seed=53).to(dtype).float()
-        y = F.layer_norm(F.gelu(a), shape, w, b, 1e-5) if mode == 2 else F.gelu(F.layer_norm(a, shape, w, b, 1e-5))
-        (y * dy).sum().backward()
-        ad, dyd = a.detach().to(a_dtype).cuda(), dy.to(dtype).cuda()
-        yd = torch.empty_like(dyd)
-        capi.adapter_norm_gelu(ad, yd, w.detach().cuda(), b.detach().cuda(), frames, P, x, mode)
-        close(yd, y, 2e-5 if dtype == torch.float32 else 2e-2, 1e-3 if dtype == torch.float32 else 2e-2, f"forward mode {mode}")
-        da = torch.empty_like(dyd)
-        dw, db = torch.empty(*shape, device="cuda"), torch.empty(*shape, device="cuda")
-        ws = torch.empty(capi.adapter_norm_gelu_bwd_workspace_bytes(frames, P, x, mode) // 4 + 4, device="cuda")
-        capi.adapter_norm_gelu_bwd(ad, dyd, da, w.detach().cuda(), b.detach().cuda(), dw, db, ws, frames, P, x, mode)
-        tol = 2e-5 if dtype == torch.float32 else 2e-2
-        close(da, a.grad, tol, 1e-3 if dtype == torch.float32 else 2e-2, f"da mode {mode}")
-        close(dw, w.grad, 1e-3 if dtype == torch.float32 else 5e-2, 1e-3, f"dweight mode {mode}")
-        close(db, b.grad, 1e-3 if dtype == torch.float32 else 5e-2, 1e-3, f"dbias mode {mode}")
+
+    def dev(t, dt, offset):  # t on the device in dt; offset: as a view that starts one element into its buffer
+        buf = torch.empty(t.numel() + offset, dtype=dt, device="cuda")
+        view = buf[offset:].view(t.shape)
+        view.copy_(t.to(dt))
+        return view
+
+    for offset in ((0, 1) if (frames, P, x) == (2, 49, 64) else (0,)):
+        want_path = ("JOINT", "ROW") if offset else ADAPTER_NORM_GELU_PATHS[(frames, P, x)]
+        want_path = getattr(capi, "ADP_" + want_path[0 if joint else 1])
+        for mode in ((1,) if joint else (0, 2)):
+            a = rnd(frames, P, x, seed=50, scale=1.5).to(a_dtype).float().requires_grad_(True)
+            shape = (P, x) if joint else (x,)
+            w = (1 + 0.1 * rnd(*shape, seed=51)).requires_grad_(True)
+            b = (0.1 * rnd(*shape, seed=52)).requires_grad_(True)
+            dy = rnd(frames, P, x, seed=53).to(dtype).float()
+            y = F.layer_norm(F.gelu(a), shape, w, b, 1e-5) if mode == 2 else F.gelu(F.layer_norm(a, shape, w, b, 1e-5))
+            (y * dy).sum().backward()
+            ad, dyd = dev(a.detach(), a_dtype, offset), dev(dy, dtype, offset)
+            yd = dev(torch.zeros_like(dy), dtype, offset)
+            what = f"mode {mode}, offset {offset}"
+            capi.adapter_norm_gelu(ad, yd, w.detach().cuda(), b.detach().cuda(), frames, P, x, mode)
+            assert capi.adapter_norm_gelu_last_path() == want_path, f"forward {what}"
+            close(yd, y, 2e-5 if dtype == torch.float32 else 2e-2, 1e-3 if dtype == torch.float32 else 2e-2, f"forward {what}")
+            da = dev(torch.zeros_like(dy), dtype, offset)
+            dw, db = torch.empty(*shape, device="cuda"), torch.empty(*shape, device="cuda")
+            ws = torch.empty(capi.adapter_norm_gelu_bwd_workspace_bytes(frames, P, x, mode) // 4 + 4, device="cuda")
+            capi.adapter_norm_gelu_bwd(ad, dyd, da, w.detach().cuda(), b.detach().cuda(), dw, db, ws, frames, P, x, mode)
+            assert capi.adapter_norm_gelu_last_path() == want_path, f"backward {what}"
+            tol = 2e-5 if dtype == torch.float32 else 2e-2
+            close(da, a.grad, tol, 1e-3 if dtype == torch.float32 else 2e-2, f"da {what}")
+            close(dw, w.grad, 1e-3 if dtype == torch.float32 else 5e-2, 1e-3, f"dweight {what}")
+            close(db, b.grad, 1e-3 if dtype == torch.float32 else 5e-2, 1e-3, f"dbias {what}")
 
 
 @pytest.mark.parametrize("name", ["tiny_ema", "tiny_rank", "tiny_pmask"])

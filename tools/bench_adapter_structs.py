@@ -7,8 +7,13 @@ new structs also the time and achieved bandwidth of each new kernel on one (laye
 `--kernel-iters` back-to-back launches on tensors of the step's shapes), against the 6.29 TB/s copy ceiling DESIGN.md
 uses.  "768-x-768-nln" (x = 256), measured in the same run, is the point of comparison.
 
+With `--kernel` the train steps are left out and one JSON line per named kernel group holds the per-kernel figures alone:
+"norm_gelu" (dfd_adapter_norm_gelu and its backward: modes 0, 1, 2 in bf16, mode 2 with an f32 `a`, mode 0 at x = 1024) or a
+struct name for that struct's kernels as above.
+
 usage: python tools/bench_adapter_structs.py [--steps 5] [--warmup 2] [--clips 16] [--frames 30] [--x 256] [--graphs]
                                              [--structs 768-x-768-nln,768-bn,768-xxx-768,linear]
+                                             [--kernel norm_gelu,768-bn,768-xxx-768,linear] [--patches 196] [--kernel-iters 20]
 """
 import argparse
 import json
@@ -46,12 +51,27 @@ def kernel_figures(struct, rows, P, T, x, iters, dev):
     out = {}
 
     def rec(name, fn, nbytes):
+        fn()  # the first launch of a kernel is not a steady-state one
         ms = timed(fn, iters)
         out[name + "_us"] = round(ms * 1e3, 1)
         out[name + "_GBps"] = round(nbytes / ms / 1e6, 1)
         out[name + "_pct_copy_ceiling"] = round(100 * nbytes / ms / 1e6 / COPY_CEILING_GBS, 1)
 
-    if struct == "768-bn":
+    if struct == "norm_gelu":
+        for name, mode, a_kw, xw in (("mode0", 0, bf, x), ("mode1", 1, bf, x), ("mode2", 2, bf, x), ("mode2_f32a", 2, f32, x),
+                                     ("mode0_x1024", 0, bf, 1024)):
+            shape = (P, xw) if mode == 1 else (xw,)
+            a, dy = torch.randn(frames, P, xw, **a_kw), torch.randn(frames, P, xw, **bf)
+            y, da = torch.empty_like(dy), torch.empty_like(dy)
+            w, b = torch.ones(*shape, **f32), torch.zeros(*shape, **f32)
+            dw, db = torch.empty_like(w), torch.empty_like(b)
+            ws = torch.empty(capi.adapter_norm_gelu_bwd_workspace_bytes(frames, P, xw, mode) // 4 + 4, **f32)
+            na, n = a.numel() * a.element_size(), dy.numel() * 2
+            rec(f"norm_gelu_fwd_{name}", lambda: capi.adapter_norm_gelu(a, y, w, b, frames, P, xw, mode), na + n)
+            # the group pass reads a and dy and writes da; the affine pass reads a and dy again
+            rec(f"norm_gelu_bwd_{name}", lambda: capi.adapter_norm_gelu_bwd(a, dy, da, w, b, dw, db, ws, frames, P, xw, mode),
+                2 * na + 3 * n)
+    elif struct == "768-bn":
         D = 768
         y, res, dout = (torch.randn(rows, D, **bf) for _ in range(3))
         stats, ws = torch.empty(2, T, **f32), torch.empty(capi.adapter_bn_workspace_bytes(frames, P, D) // 4 + 4, **f32)
@@ -83,10 +103,18 @@ def main():
     ap.add_argument("--kernel-iters", type=int, default=20)
     ap.add_argument("--graphs", action="store_true", help="Detector.static_graphs (HIP-graph replay of decoder + adapter)")
     ap.add_argument("--structs", default="768-x-768-nln,768-bn,768-xxx-768,linear")
+    ap.add_argument("--kernel", default="", help="per-kernel figures only: norm_gelu and / or struct names, comma-separated")
+    ap.add_argument("--patches", type=int, default=196, help="patches per frame of the --kernel tensors")
     a = ap.parse_args()
     logging.getLogger().setLevel(logging.ERROR)
     dev = "cuda:0"
     B, T = a.clips, a.frames
+    for group in filter(None, a.kernel.split(",")):
+        line = {"workload": "adapter_kernels", "kernel": group, "frames": B * T, "patches": a.patches, "x": a.x, "iters": a.kernel_iters}
+        line.update(kernel_figures(group, B * T * a.patches, a.patches, T, a.x, a.kernel_iters, dev))
+        print(json.dumps(line), flush=True)
+    if a.kernel:
+        return
     for struct in a.structs.split(","):
         cfg = make_config("ViT-B/16", decode_mode="stride", decode_stride=2, adapter__type="normal", adapter__frozen=0,
                           adapter__struct={"type": struct, "x": a.x})
