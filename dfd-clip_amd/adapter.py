@@ -146,7 +146,8 @@ class CompInvAdapter(RuntimeStateMixin, nn.Module):
         return out
 
     def _weights(self, act):
-        key = (act, tuple(p._version for p in self.parameters()))
+        # (the address too: `p.data = new` — the unfused EMA teacher's update — re-seats a parameter without moving its version)
+        key = (act, tuple((p._version, p.data_ptr()) for p in self.parameters()))
         if self._prep is None or self._prep[0] != key:
             w = {}
             for i in range(self.n_layers):

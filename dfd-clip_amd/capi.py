@@ -236,6 +236,11 @@ KVGATHER_SIGNATURES = {
     "dfd_kv_gather_last_path": (c_int, []),
 }
 
+# the EMA-teacher update beside the ABI, in a header of its own (include/dfdclip_ema.h)
+EMA_SIGNATURES = {
+    "dfd_ema_step": (c_int, [c_void_p, c_int, c_int64, c_float, c_float, c_void_p]),
+}
+
 # test / measurement hooks outside the ABI header (include/dfdclip_hooks.h)
 class AttentionPlan(Structure):
     """dfd_attention_plan_t (include/dfdclip_hooks.h)."""
@@ -304,7 +309,7 @@ def load_library(path=None):
     lib = ctypes.CDLL(path)
     for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **EXPLAIN_SIGNATURES, **AUGMENT_SIGNATURES, **ALIGN_SIGNATURES,
                                **ELASTIC_SIGNATURES, **YUV_SIGNATURES, **SWIGLU_SIGNATURES, **KVGATHER_SIGNATURES,
-                               **HOOK_SIGNATURES}.items():
+                               **EMA_SIGNATURES, **HOOK_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError:
@@ -1122,6 +1127,48 @@ def sgd_step(table, n, total_blocks, lr, momentum, weight_decay, first_step, ext
     assert table.dtype == torch.int64 and table.is_contiguous() and table.shape == (n, 7)
     _check(load_library().dfd_sgd_step(_ptr(table), int(n), int(total_blocks), float(lr), float(momentum), float(weight_decay),
                                        1 if first_step else 0, _stream(), None if extra is None else ctypes.byref(extra)), "dfd_sgd_step")
+
+
+def ema_factors(ratio):
+    """(keep, take) of `ema_step`: the Python doubles 1 - r and r, which torch casts to f32 inside `(1 - r) * t + r * s`."""
+    r = float(ratio)
+    return 1.0 - r, r
+
+
+def ema_step(table, n, total_blocks, ratio, table_host=None):
+    """t <- (1 - ratio) t + ratio s over every entry of `table`, in one launch (include/dfdclip_ema.h).  `table`: device int64
+    tensor [n, 7] laid out as dfd_sgd_param (`sgd_step`): p = the teacher's parameter, g = the student's, buf = 0, mirror =
+    the teacher's transposed copy or 0.  Raises before the launch when an entry's p and g are one address, has a `buf` or
+    a null pointer: `table_host` is the host copy to look at — without it the device table is copied back, which synchronises."""
+    _dev(table)
+    if table.dtype != torch.int64 or not table.is_contiguous() or table.dim() != 2 or tuple(table.shape) != (int(n), 7) or n <= 0:
+        raise DfdError(f"ema_step: empty table, or not a contiguous int64 [n, 7] tensor (n={n}, table {tuple(table.shape)} {table.dtype})")
+    host = table.cpu() if table_host is None else table_host
+    if tuple(host.shape) != (int(n), 7):
+        raise DfdError(f"ema_step: table_host is {tuple(host.shape)}, the table [{n}, 7]")
+    if bool((host[:, 0] == host[:, 1]).any()):
+        raise DfdError("ema_step: an entry blends a tensor with itself (p == g): (1 - r) x + r x is not x in f32; skip the pair")
+    if bool((host[:, 0] == 0).any() or (host[:, 1] == 0).any() or (host[:, 2] != 0).any()):
+        raise DfdError("ema_step: every entry needs p and g, and buf must be NULL")
+    keep, take = ema_factors(ratio)
+    _check(load_library().dfd_ema_step(_ptr(table), int(n), int(total_blocks), keep, take, _stream()), "dfd_ema_step")
+
+
+def ema_reference(t, s, ratio):
+    """What `ema_step` leaves in `t`'s place, restated op for op on NumPy arrays or torch tensors (any device): both
+    products rounded to f32, then the sum — fadd(fmul(f32(1 - r), t), fmul(f32(r), s)).  Returns a new f32 array / tensor."""
+    keep, take = ema_factors(ratio)
+    if torch.is_tensor(t):
+        k = torch.tensor(keep, dtype=torch.float32, device=t.device)
+        r = torch.tensor(take, dtype=torch.float32, device=t.device)
+        a = torch.mul(t.to(torch.float32), k)
+        b = torch.mul(s.to(torch.float32), r)
+        return torch.add(a, b)
+    import numpy as np
+    with np.errstate(all="ignore"):
+        a = np.multiply(np.asarray(t, dtype=np.float32), np.float32(keep), dtype=np.float32)
+        b = np.multiply(np.asarray(s, dtype=np.float32), np.float32(take), dtype=np.float32)
+        return np.add(a, b, dtype=np.float32)
 
 
 def layernorm_bwd(x, gamma, dy, dx, dgamma, dbeta, xhat_ws, accumulate_dx=False, eps=1e-5):

@@ -3,7 +3,7 @@
 // over the adapter (src/models.py:1053-1057).  One launch per step where torch's multi-tensor paths take several (SGD ten;
 // AdamW: tools/bench_adamw.py counts them), and for the decoder's Linear weights the launch also rewrites the transposed
 // f32 copy the row-streaming linear kernels read (dfd_linear_rows_t): the 20 transposes a training step otherwise needs
-// after every update disappear.
+// after every update disappear.  The EMA teacher's update (dfd_ema_step, include/dfdclip_ema.h) walks the same table.
 //
 // SGD's arithmetic, per element, in torch's order (torch/optim/sgd.py, foreach path; AdamW's stands at its kernel):
 //     g   = grad + wd * p                (one fused multiply-add)
@@ -16,6 +16,7 @@
 #include <cstddef>
 
 #include "stream_policy.hpp"
+#include "../../include/dfdclip_ema.h"
 
 namespace {
 
@@ -120,6 +121,27 @@ __global__ __launch_bounds__(256) void adamw_step_kernel(const SgdEntry* __restr
   });
 }
 
+// The teacher's exponential moving average (reference src/trainer.py:179-185: p_t <- (1 - r) p_t + r p) over the same table:
+// `p` the teacher's parameter, `g` the student's, `buf` unused.  torch evaluates the expression on f32 tensors as two
+// products, each rounded, and one sum: contracted into a fused multiply-add the result differs in the last bit, so
+// contraction is switched off for exactly this expression.
+__device__ __forceinline__ float ema_blend(float keep, float t, float take, float s) {
+#pragma clang fp contract(off)
+  const float a = keep * t;
+  const float b = take * s;
+  return a + b;
+}
+
+template <bool NT>
+__global__ __launch_bounds__(256) void ema_step_kernel(const SgdEntry* __restrict__ table, int n, float keep, float take) {
+  __shared__ float tile[32][33];
+  step_entries<NT>(table, n, tile, [&](int, const SgdEntry& e, int64_t i) {
+    const float nt = ema_blend(keep, stream_load4<NT>(e.p + i), take, stream_load4<NT>(e.g + i));
+    stream_store4<NT>(e.p + i, nt);
+    return nt;
+  });
+}
+
 }  // namespace
 
 static_assert(sizeof(SgdEntry) == sizeof(dfd_sgd_param), "dfd_sgd_param layout");
@@ -166,5 +188,18 @@ extern "C" int dfd_sgd_step(const dfd_sgd_param* table_dev, int n, int64_t total
   hipLaunchKernelGGL(nt ? adamw_step_kernel<true> : adamw_step_kernel<false>, dim3((unsigned)total_blocks), dim3(256), 0, static_cast<hipStream_t>(stream), table, n,
                      extra->exp_avg_sq, a);
   DFD_CHECK_LAUNCH("dfd_sgd_step");
+  return DFD_OK;
+}
+
+extern "C" int dfd_ema_step(const dfd_sgd_param* table_dev, int n, int64_t total_blocks, float keep, float take, void* stream) {
+  DFD_REQUIRE(table_dev != nullptr && n > 0, "dfd_ema_step: empty table (table=%p, n=%d)", (const void*)table_dev, n);
+  DFD_REQUIRE(total_blocks > 0 && total_blocks < ((int64_t)1 << 31), "dfd_ema_step: total_blocks = %lld outside [1, 2^31)",
+              (long long)total_blocks);
+  DFD_REQUIRE(std::isfinite(keep) && std::isfinite(take), "dfd_ema_step: non-finite factor (keep=%g, take=%g)", (double)keep, (double)take);
+  const auto* table = reinterpret_cast<const SgdEntry*>(table_dev);
+  const bool nt = dfd_stream_on(DFD_STREAM_OPTIMIZER);
+  hipLaunchKernelGGL(nt ? ema_step_kernel<true> : ema_step_kernel<false>, dim3((unsigned)total_blocks), dim3(256), 0, static_cast<hipStream_t>(stream), table, n,
+                     keep, take);
+  DFD_CHECK_LAUNCH("dfd_ema_step");
   return DFD_OK;
 }

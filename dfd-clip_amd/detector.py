@@ -73,6 +73,76 @@ def gather_reference(k, v, index, pos, T, P=None):
     return outs[0], outs[1]
 
 
+class EncodedClips:
+    """One encoder pass over a batch of clips, held for more than one consumer (`Detector.encode_clips`): the student of a
+    teacher-mode training step and its EMA teacher share the frozen tower, so the teacher reads the K/V the student's pass
+    has just produced instead of running the tower again.
+
+    kv        the raw source as `_encode` returned it, positional embedding NOT applied by any consumer yet: strided views
+              [L, B*T, P, D] of the tapped layers' q|k|v activations (`layout == "in_place"`) or the dense raw export
+              [L, B*T*P, D] (`layout == "dense"`)
+    pipe      the pipeline context of a pipelined pass (caller's stream + the K/V set's three reader events) or None
+    b, t      clips and frames per clip of the pass (after `op_mode.ema_frame`); `in_shape` the shape `encode_clips` was given
+    tower     the encoder that ran: a consumer must hold this very object
+    generation  the producer's pass counter at this pass; a handle of an earlier pass is stale
+
+    Order: consumers run on the stream `encode_clips` was called on.  Other detectors read first; the PRODUCER's own
+    `predict(..., encoded=)` / `forward(..., encoded=)` comes last — it records the K/V set's reader events exactly as a
+    forward without a handle does, so everything queued before it is ordered before the next pass into that set.  A
+    producer that does not consume its handle calls `release()`, which records the events; until one of the two happened
+    the producer's next `encode_clips` (or plain forward) raises."""
+
+    def __init__(self, producer, kind, kv, pipe, in_shape, shape, train, device):
+        self.producer, self.kind, self.kv, self.pipe = producer, kind, kv, pipe
+        self.in_shape, self.shape, self.train, self.device = tuple(in_shape), tuple(shape), bool(train), device
+        self.b, self.t = int(shape[0]), int(shape[1])
+        self.grad = torch.is_grad_enabled()
+        self.layout = "in_place" if kv[0].dim() == 4 else "dense"
+        self.tower = producer.encoder
+        self.generation = producer._enc_generation
+        self.consumed = False
+
+    def _check(self, consumer, x, train):
+        """Raises unless `consumer` may read this pass for input `x` now.  -> True for the producer itself."""
+        if consumer.encoder is not self.tower:
+            raise capi.DfdError("encoded=: this handle is another tower's pass (a consumer must share the producer's encoder object: "
+                                "EmaTeacher(share_encoder=True))")
+        if self.generation != self.producer._enc_generation:
+            raise capi.DfdError(f"encoded=: stale handle (pass {self.generation}, the producer is at pass {self.producer._enc_generation}): "
+                                "its K/V set may hold a later batch")
+        if self.consumed:
+            raise capi.DfdError("encoded=: the producer has consumed or released this handle: the next pass may already be writing its K/V set")
+        if tuple(x.shape) not in (self.in_shape, self.shape):
+            raise capi.DfdError(f"encoded=: the handle is a pass over clips of shape {self.in_shape}, not {tuple(x.shape)}")
+        own = consumer is self.producer
+        if own and (bool(train) != self.train or torch.is_grad_enabled() != self.grad):
+            raise capi.DfdError(f"encoded=: the pass was made for train={self.train}, grad={self.grad}; consume it in the same mode")
+        if not own and self.pipe is not None and torch.cuda.current_stream() != self.pipe[0]:
+            raise capi.DfdError("encoded=: consumers run on the stream encode_clips was called on")
+        return own
+
+    def _take(self, kind):
+        """The producer's own consumption: what `_encode` returned, once."""
+        if kind != self.kind:
+            raise capi.DfdError(f"encoded=: the pass was made for the {self.kind!r} path, the forward takes the {kind!r} one")
+        self.consumed = True
+        if self.producer._enc_open is self:
+            self.producer._enc_open = None
+        return self.kv, self.pipe
+
+    def release(self):
+        """The producer will not consume this pass: record the K/V set's reader events behind whatever has been queued on
+        the caller's stream, and let the producer encode again.  A no-op once consumed or released."""
+        if self.consumed:
+            return
+        self.consumed = True
+        if self.pipe is not None:
+            for ev in self.pipe[1:]:
+                ev.record(self.pipe[0])
+        if self.producer._enc_open is self:
+            self.producer._enc_open = None
+
+
 class TaskLoss:
     """Unreduced loss of one task head: `loss(logits [B, out_dim], labels) -> [B]`.  The trainer takes the mean itself
     (reference `src/trainer.py:154-155`); the config names a loss by the reference's factory name, optionally with
@@ -245,7 +315,8 @@ class ClipTransform:
 
 class Detector(RuntimeStateMixin, nn.Module):
     _RUNTIME_STATE = {"_kv_static": None, "_kv_cache": {}, "_enc_stream": None, "_pipe_events": [[], []], "_pipe_step": 0, "_pos_snap": None,
-                      "_mask_tables": None, "_mask_step": 0, "_last_masked_kv": None, "_last_masked_src": None, "_drop_master": None, "_enc_graphs": {}, "_enc_graph_seen": {}, "_enc_graphs_failed": None, "_all_params": None}
+                      "_mask_tables": None, "_mask_step": 0, "_last_masked_kv": None, "_last_masked_src": None, "_drop_master": None, "_enc_graphs": {}, "_enc_graph_seen": {}, "_enc_graphs_failed": None, "_all_params": None,
+                      "_enc_open": None, "_enc_generation": 0, "_identity_tables": {}}
 
     def _apply(self, fn, *a, **k):
         self._all_params = None  # (.to() / .half() may re-create parameter objects)
@@ -350,6 +421,8 @@ class Detector(RuntimeStateMixin, nn.Module):
         self._mask_tables, self._mask_step = None, 0
         self._keep_masked_kv = False  # tests: keep what a masked forward gathered in `_last_masked_kv`, and from where in `_last_masked_src`
         self._last_masked_kv = self._last_masked_src = None
+        # `encode_clips`: the handle the producer has not consumed yet, the pass counter, identity index tables for consumers
+        self._enc_open, self._enc_generation, self._identity_tables = None, 0, {}
         # train-mode dropout (reference models.py:163, :294, :304, :804-912; every configs/deepfake/*.yaml sets 0.5):
         # counter-based masks from a device-resident {seed, step}; see `seed_dropout`
         self.dropout_p = float(config.dropout) if "dropout" in config else 0.0
@@ -632,7 +705,7 @@ class Detector(RuntimeStateMixin, nn.Module):
         ev.record()
         return host, dev
 
-    def _masked_kv_device(self, x, t, pos, drop_rng):
+    def _masked_kv_device(self, x, t, pos, drop_rng, encoded=None):
         """Patch-masked training on the fast path (models.py:511-544) -> the (k, v) the decoder reads, [L, B*T*S, D].
 
         The encoder pass goes through `_encode` like an unmasked one — K/V in place (no export written), persistent sets,
@@ -646,8 +719,11 @@ class Detector(RuntimeStateMixin, nn.Module):
         self._last_mask_path = "device"
         patches = (self.encoder.input_resolution // self.encoder.patch_size) ** 2
         num_select = int(patches * self.train_mode.patch_mask.ratio)
-        host, index = self._mask_table(patches, num_select, x.device)
-        src, pipe = self._encode(x, t, None, keep=True, allow_in_place=bool(self.kv_in_place))
+        host, index = self._mask_table(patches, num_select, x.device if encoded is None else encoded.device)
+        if encoded is None:
+            src, pipe = self._encode(x, t, None, keep=True, allow_in_place=bool(self.kv_in_place))
+        else:
+            src, pipe = encoded._take("masked")  # (this model's own pass, made by `encode_clips`)
         kr, vr = capi.kv_gather_patches(src[0], src[1], index, pos if self.adapter is None else None, T=t, P=patches, index_host=host)
         if pipe is not None:
             for ev in pipe[1:]:
@@ -662,12 +738,94 @@ class Detector(RuntimeStateMixin, nn.Module):
         finally:
             self.adapter.patches = patches
 
-    def predict(self, x, m, with_video_features=False, with_adapt_features=False, train=False, with_attention=False):
+    def encode_clips(self, x, train=False):
+        """The encoder pass of `forward(x, ..., train=train)` on its own -> an `EncodedClips` that this model's
+        `predict` / `forward` (`encoded=`) and those of a model sharing its tower (an `EmaTeacher(share_encoder=True)`)
+        consume instead of running the tower again.  Everything `forward` does to `x` up to and including `_encode` happens
+        here, in the mode this model would take: `op_mode.ema_frame`, K/V in place or the dense raw export, persistent sets,
+        the pipelined stream and the encoder graph where those are on.  Call it in the grad mode of the forward that will
+        consume it.  The producer consumes the handle last, or calls its `release()`, before it encodes again."""
+        if self._enc_open is not None:
+            raise capi.DfdError("encode_clips: the previous handle is still open: this model must consume it (predict / forward with "
+                                "encoded=) or release() it before the next pass overwrites its K/V")
+        if x.dim() != 5:
+            raise capi.DfdError(f"encode_clips: clips [B,T,3,H,W], got {tuple(x.shape)}")
+        in_shape = tuple(x.shape)
+        x, _ = self._ema_frames(x, None)
+        b, t = x.shape[:2]
+        if t != self.num_frames and self.decoder.positional_embedding is not None:
+            raise RuntimeError(f"The size of tensor a ({t}) must match the size of tensor b ({self.num_frames}) "
+                               "at non-singleton dimension 1 (temporal positional embedding)")
+        masked = train and "patch_mask" in self.train_mode
+        if self.adapter is None and not self.kv_in_place:
+            raise capi.DfdError("encode_clips: kv_in_place = False without an adapter bakes this model's positional embedding into the "
+                                "export, which no other consumer can read; leave kv_in_place on")
+        if masked and self.mask_gather != "device":
+            raise capi.DfdError(f"encode_clips: patch-masked training shares its pass through mask_gather='device' only (got {self.mask_gather!r})")
+        if self.adapter is None and not masked:
+            kind = "plain"
+            kv, pipe = self._encode(x, t, self.decoder.temporal_pos(), keep=bool(self.static_graphs and train))
+        elif masked:
+            kind = "masked"
+            kv, pipe = self._encode(x, t, None, keep=True, allow_in_place=bool(self.kv_in_place))
+        else:
+            kind = "adapter"
+            kv, pipe = self._encode(x, t, None, keep=bool(self.static_graphs and train and torch.is_grad_enabled()), allow_in_place=False)
+        self._enc_generation += 1
+        self._enc_open = EncodedClips(self, kind, kv, pipe, in_shape, x.shape, train, x.device)
+        return self._enc_open
+
+    def _identity_table(self, layers, patches, device):
+        """(host, device) int32 [L, P] table that keeps every patch row in order: `dfd_kv_gather_patches` with it turns an
+        in-place K/V set into the dense raw export an adapter reads."""
+        key = (layers, patches, device)
+        if key not in self._identity_tables:
+            host = torch.arange(patches, dtype=torch.int32).repeat(layers, 1).contiguous()
+            self._identity_tables[key] = (host, host.to(device))
+        return self._identity_tables[key]
+
+    def _derive_kv(self, encoded, t, pos, drop_rng, masked):
+        """What the decoder of THIS model reads from another model's pass over the shared tower (an unmasked forward: the
+        teacher's), by the producer's layout:
+          in place, no adapter here   the same set in place, this model's positional embedding added on the fly
+          dense raw export            (a copy of it, see below) into this model's adapter
+          in place, adapter here      dense raw rows from ONE dfd_kv_gather_patches launch (identity table, no positional
+                                      add), into this model's adapter
+        Nothing is recorded on the K/V set's events: the producer consumes after this, on the same stream."""
+        if masked:
+            raise capi.DfdError("encoded=: a patch-masked forward reads its own model's pass only")
+        k, v = encoded.kv[0], encoded.kv[1]
+        if self.adapter is None:
+            if encoded.layout != "in_place":
+                raise capi.DfdError("encoded=: a model without an adapter reads K/V in place; the handle holds a dense export")
+            return k, v, pos
+        if encoded.layout == "in_place":
+            host, index = self._identity_table(k.shape[0], k.shape[2], k.device)
+            k, v = capi.kv_gather_patches(k, v, index, None, T=t, P=k.shape[2], index_host=host)
+        elif not (torch.is_grad_enabled() and any(p.requires_grad for p in self.adapter.parameters())):
+            # without autograd the adapter works IN PLACE on what it is handed, and the producer has yet to read its export:
+            # this consumer gets a copy (two device copies where a pass through the tower was)
+            k, v = k.clone(), v.clone()
+        return self.adapter.run(k, v, t, pos, drop_rng)
+
+    def predict(self, x, m, with_video_features=False, with_adapt_features=False, train=False, with_attention=False, encoded=None):
         """x [B,T,3,R,R], m [B,T] bool -> (task_logits list of [B,out_dim] with L2 norm 5, features).
         `with_attention`: features["attention"] = per tapped layer the f32 [B, heads, T, patches] weight that the decoder
         block applied to each key's value, ½(softmax + CoDA) (CoDA weights can be negative); padded frames are 0.  The
-        no-grad forward only; the logits are the bits of the same call without it."""
+        no-grad forward only; the logits are the bits of the same call without it.
+        `encoded`: an `EncodedClips` of these clips (`encode_clips`, of this model or of one that shares its tower): the tower
+        is not run, `x` is used for its shape only, and K/V are derived from the handle's raw source with THIS model's
+        positional embedding, adapter and mask table.  The dropout counter advances as without a handle."""
         b, t, c, h, w = x.shape
+        own, device = False, x.device
+        if encoded is not None:
+            own = encoded._check(self, x, train)
+            b, t, device = encoded.b, encoded.t, encoded.device
+            if tuple(m.shape) != (b, t):
+                raise capi.DfdError(f"encoded=: the handle holds {b} clips of {t} frames, the frame mask is {tuple(m.shape)}")
+        elif self._enc_open is not None:
+            raise capi.DfdError("a handle of encode_clips is still open: consume it (predict / forward with encoded=) or release() it "
+                                "before the next encoder pass overwrites its K/V")
         if t != self.num_frames and self.decoder.positional_embedding is not None:
             raise RuntimeError(f"The size of tensor a ({t}) must match the size of tensor b ({self.num_frames}) "
                                "at non-singleton dimension 1 (temporal positional embedding)")
@@ -678,14 +836,18 @@ class Detector(RuntimeStateMixin, nn.Module):
         if self.adapter is not None:
             self.adapter.use_graphs = False
         pipe = None
-        drop_rng = self._next_drop_rng(x.device)
+        drop_rng = self._next_drop_rng(device)
         masked = train and "patch_mask" in self.train_mode
-        if self.adapter is None and not masked:
+        if encoded is not None and not own:
+            kv = self._derive_kv(encoded, t, pos, drop_rng, masked)
+        elif self.adapter is None and not masked:
             self.decoder.use_graphs = bool(self.static_graphs and train)
-            kv, pipe = self._encode(x, t, pos, keep=bool(self.static_graphs and train))
+            kv, pipe = self._encode(x, t, pos, keep=bool(self.static_graphs and train)) if encoded is None else encoded._take("plain")
         elif masked and self.mask_gather == "device":
-            kv = self._masked_kv_device(x, t, pos, drop_rng)
+            kv = self._masked_kv_device(x, t, pos, drop_rng, encoded)
         elif masked:
+            if encoded is not None:
+                raise capi.DfdError("encoded=: patch-masked training reads a handle through mask_gather='device' only")
             if self.mask_gather != "torch":
                 raise ValueError(f"mask_gather={self.mask_gather!r}: 'device' or 'torch'")
             self._last_mask_path = "torch"
@@ -725,7 +887,7 @@ class Detector(RuntimeStateMixin, nn.Module):
             # adapter's parameters when they are trainable
             graphs = bool(self.static_graphs and train and torch.is_grad_enabled())
             self.adapter.use_graphs = self.decoder.use_graphs = graphs
-            kv, pipe = self._encode(x, t, None, keep=graphs, allow_in_place=False)
+            kv, pipe = self._encode(x, t, None, keep=graphs, allow_in_place=False) if encoded is None else encoded._take("adapter")
             if pipe is not None:
                 self.adapter._after_backward = pipe[3].record  # its backward is the last reader of the raw export
             kv = self.adapter.run(kv[0], kv[1], t, pos, drop_rng)
@@ -788,19 +950,32 @@ class Detector(RuntimeStateMixin, nn.Module):
         logging.info("adapter %s: %s", config.adapter.struct.type, "fresh parameters" if kind == "normal" else f"parameters of {config.adapter.path}")
         return adapter
 
-    def forward(self, x, y, m, comp=None, speed=None, train=False, single_task=None, *args, **kargs):
+    def _ema_frames(self, x, m):
+        """`op_mode.ema_frame`: exponential moving average of the frames -> one frame per clip and its mask column
+        (models.py:572-578); uint8 clips go through the transform first.  Without the mode: (x, m) as they are."""
+        if not ("ema_frame" in self.op_mode and self.op_mode.ema_frame):
+            return x, m
         b, t, c, h, w = x.shape
-        if "ema_frame" in self.op_mode and self.op_mode.ema_frame:
-            if x.dtype == torch.uint8:
-                x = self.transform(x)
-                h, w = x.shape[-2:]
-            # exponential moving average of the frames -> one frame per clip (models.py:572-578)
-            r = self.op_mode.ema_frame
-            _x = torch.zeros((b, 1, c, h, w), device=x.device)
-            for i in range(t):
-                _x = _x * r + x[:, i].unsqueeze(1) * (1 - r)
-            x, m = _x, m[:, 0].unsqueeze(1)
-        task_logits, features = self.predict(x, m, with_video_features=True, train=train)
+        if x.dtype == torch.uint8:
+            x = self.transform(x)
+            h, w = x.shape[-2:]
+        r = self.op_mode.ema_frame
+        _x = torch.zeros((b, 1, c, h, w), device=x.device)
+        for i in range(t):
+            _x = _x * r + x[:, i].unsqueeze(1) * (1 - r)
+        return _x, (None if m is None else m[:, 0].unsqueeze(1))
+
+    def forward(self, x, y, m, comp=None, speed=None, train=False, single_task=None, *args, encoded=None, **kargs):
+        b = x.shape[0]
+        if encoded is None:
+            x, m = self._ema_frames(x, m)
+        else:
+            # the pass (frame average included) is the handle's: x is looked at for its shape only
+            if tuple(x.shape) != encoded.in_shape:
+                raise capi.DfdError(f"encoded=: the handle is a pass over clips of shape {encoded.in_shape}, not {tuple(x.shape)}")
+            if "ema_frame" in self.op_mode and self.op_mode.ema_frame:
+                m = m[:, 0].unsqueeze(1)
+        task_logits, features = self.predict(x, m, with_video_features=True, train=train, encoded=encoded)
         video_features = features["video"]
         task_losses = [
             loss_fn(logits, labels) if single_task == None or i == single_task else 0

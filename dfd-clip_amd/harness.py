@@ -30,11 +30,15 @@ code, so that a reference user finds the same step semantics on top of `Detector
                   mean over clips -> probability of class 1.
 """
 import copy
+import logging
 
 import torch
 from torch.optim.lr_scheduler import OneCycleLR
 
+from . import capi
 from . import dist as ddist
+
+_log = logging.getLogger(__name__)
 
 
 def make_one_cycle(optimizer, learning_rate, max_steps, num_processes=None):
@@ -50,29 +54,112 @@ def step_scheduler(scheduler, num_processes=None):
 class EmaTeacher:
     """EMA copy of the model that labels the tasks a batch does not cover (reference
     `src/trainer.py:66-69` deep copy, `:179-185` update p_t <- (1-r) p_t + r p, `:188-190` teaching
-    starts once `teach_at < steps`, `:124-137` pseudo labels = softmax of the teacher's logits)."""
+    starts once `teach_at < steps`, `:124-137` pseudo labels = softmax of the teacher's logits).
 
-    def __init__(self, model, ema_ratio, teach_at):
-        self.module = copy.deepcopy(model)
+    Two opt-in switches take the mode onto the fast path; with both off this is the reference's loop, op for op.
+
+    `share_encoder`: the copy keeps the model's frozen tower instead of duplicating it (`teacher.module.encoder is
+    model.encoder`: one set of tower parameters, staged operands and fp8 scales), `update` leaves the shared parameters
+    alone, and `train_step` runs ONE encoder pass per batch that teacher and student both read (`Detector.encode_clips`).
+    The reference blends its copy of the tower with the tower it was copied from every step; in f32 that self-blend is
+    not the identity ((1 - r) x + r x != x for about one element in six at r = 0.999, exact at r = 0.5), so its teacher's tower
+    drifts from the frozen weights by rounding.  Here the teacher reads the frozen tower itself: the one deliberate deviation.
+
+    `fused`: `update` is one `dfd_ema_step` launch over every parameter pair that is contiguous f32 on the GPU, in place —
+    the teacher's parameters keep their addresses, its decoder's transposed weight copies are rewritten by the same launch
+    (no transpose runs afterwards) and version-keyed caches see the change.  The arithmetic is the torch expression's, bit
+    for bit.  Pairs the kernel does not cover are blended by the torch expression (in place) and logged once."""
+
+    def __init__(self, model, ema_ratio, teach_at, share_encoder=False, fused=False):
+        self.share_encoder = bool(share_encoder)
+        self.fused = bool(fused)
+        if self.share_encoder:
+            tower = model.encoder
+            self.module = copy.deepcopy(model, memo={id(tower): tower})
+        else:
+            self.module = copy.deepcopy(model)
         self.ema_ratio = float(ema_ratio)
         self.teach_at = int(teach_at)
         self.steps = 0
         self.teaching = False
+        self._pairs = None   # fused: (student model, [(teacher parameter, student parameter), ...] without aliased pairs)
+        self._plan = None
+        self._told = False
 
     @torch.no_grad()
     def update(self, model):
         r = self.ema_ratio
-        for p1, p2 in zip(self.module.parameters(), model.parameters()):
-            p1.data = (1 - r) * p1.data + r * p2.data
+        if self.fused:
+            self._update_fused(model, r)
+        else:
+            for p1, p2 in zip(self.module.parameters(), model.parameters()):
+                if p1 is p2:
+                    continue  # share_encoder: the tower is the student's own; re-seating its .data would re-seat the student's
+                p1.data = (1 - r) * p1.data + r * p2.data
         self.steps += 1
         if not self.teaching and self.teach_at < self.steps:
             self.teaching = True
 
+    # ---- fused update: one dfd_ema_step launch ------------------------------------------------------------------------
+    @staticmethod
+    def _fusable(p1, p2):
+        return all(p.dtype == torch.float32 and p.is_cuda and p.is_contiguous() for p in (p1, p2)) and p1.shape == p2.shape \
+            and p1.device == p2.device and p1.data_ptr() != p2.data_ptr() and p1.numel() > 0
+
+    def _ema_plan(self, pairs):
+        """Device table of the pairs the kernel covers (+ the pairs it does not), planned once and again when a parameter's
+        address or a transposed copy changed — `optim._TablePlans._plan`'s rule."""
+        mirrors = getattr(self.module, "decoder", None)
+        if not hasattr(mirrors, "mirror_for"):
+            mirrors = None
+        key = tuple((p1.data_ptr(), p2.data_ptr(), tuple(p1.shape)) for p1, p2 in pairs)
+        plan = self._plan
+        if plan is not None and plan["key"] == key and all(
+                e[2] is None or mirrors.current_mirror(e[0]) is e[2] for e in plan["entries"]):
+            return plan
+        entries, rest, rows, first = [], [], [], 0
+        for p1, p2 in pairs:
+            if not self._fusable(p1, p2) or (entries and p1.device != entries[0][0].device):
+                rest.append((p1, p2))
+                continue
+            m = mirrors.mirror_for(p1) if (mirrors is not None and p1.dim() == 2) else None
+            nr, nc = p1.shape if m is not None else (0, 0)
+            entries.append((p1, p2, m))
+            rows.append([p1.data_ptr(), p2.data_ptr(), 0, 0 if m is None else m.data_ptr(), p1.numel(), int(nr) | (int(nc) << 32), first])
+            first += capi.sgd_blocks(p1.numel(), nr, nc, m is not None)
+        host = torch.tensor(rows, dtype=torch.int64).view(-1, 7)
+        plan = dict(key=key, entries=entries, rest=rest, host=host, table=host.to(entries[0][0].device) if entries else None,
+                    blocks=first, params=[e[0] for e in entries], written=[(e[0], e[2]) for e in entries if e[2] is not None],
+                    mirrors=mirrors)
+        self._plan = plan
+        return plan
+
+    def _update_fused(self, model, r):
+        if self._pairs is None or self._pairs[0] is not model:  # the module trees are static: walk them once
+            self._pairs = (model, [(p1, p2) for p1, p2 in zip(self.module.parameters(), model.parameters()) if p1 is not p2])
+        plan = self._ema_plan(self._pairs[1])
+        if plan["entries"]:
+            capi.ema_step(plan["table"], len(plan["entries"]), plan["blocks"], r, table_host=plan["host"])
+            # the kernel wrote through raw pointers: caches keyed on a parameter's version counter must see the update
+            # (the call takes an ITERABLE of tensors), and the transposed copies it rewrote are current
+            torch._C._increment_version(plan["params"])
+            if plan["written"]:
+                plan["mirrors"].mirrors_written(plan["written"])
+        if plan["rest"]:
+            if not self._told:
+                self._told = True
+                _log.warning("EmaTeacher(fused=True): %d parameter pair(s) are not contiguous f32 on one GPU: blended with torch's "
+                             "own kernels", len(plan["rest"]))
+            for p1, p2 in plan["rest"]:
+                p1.data.copy_((1 - r) * p1.data + r * p2.data)
+
     @torch.no_grad()
-    def labels(self, frames, mask, labels, task_index, total_tasks):
+    def labels(self, frames, mask, labels, task_index, total_tasks, encoded=None):
         """Per-task label list: the batch's own labels for its task, the teacher's class probabilities
-        for every other task (the model's losses accept probability targets)."""
-        _, teacher_logits = self.module(frames, [None] * total_tasks, mask, single_task=-1)
+        for every other task (the model's losses accept probability targets).  `encoded`: the student's
+        `Detector.encode_clips` handle of these frames — the teacher then runs no encoder pass of its own (`share_encoder`)."""
+        extra = {} if encoded is None else {"encoded": encoded}
+        _, teacher_logits = self.module(frames, [None] * total_tasks, mask, single_task=-1, **extra)
         return [labels if i == task_index else teacher_logits[i].softmax(dim=-1) for i in range(total_tasks)]
 
 
@@ -98,7 +185,9 @@ def train_step(model, optimizer, batches, scheduler=None, total_tasks=None, teac
     """One optimizer step over `batches`: list of (frames, labels, mask, comps, speed, task_index)
     — one entry per training set, as the reference draws one batch per set per step.
     With an `EmaTeacher` that has started teaching, every task contributes a loss (the other tasks
-    against the teacher's soft labels); the teacher is updated after the optimizer step.
+    against the teacher's soft labels); the teacher is updated after the optimizer step.  A teaching teacher built with
+    `share_encoder` labels each batch from the student's own encoder pass (`Detector.encode_clips` -> `teacher.labels(...,
+    encoded=)` -> `model(..., encoded=)`): one pass through the frozen tower per batch instead of two.
     `augment`: an `augment.ClipAugment`; each batch's uint8 device frames go through it (one fresh draw per batch) before
     the model and the teacher see them, as the reference's datasets augment before collation.
     `ssl_fake`: an `elastic.SslFake`; after `augment` (the reference's order, `src/datasets.py:665-668`) each batch's real
@@ -109,17 +198,28 @@ def train_step(model, optimizer, batches, scheduler=None, total_tasks=None, teac
     model.train()
     out = {"losses": [], "logits": []}
     teaching = teacher is not None and teacher.teaching
+    shared = teaching and bool(getattr(teacher, "share_encoder", False))
     for frames, labels, mask, comps, speed, task_index in batches:
         if augment is not None:
             frames = _augmented(frames, augment)
         if ssl_fake is not None:
             frames, labels = _ssl_faked(frames, labels, ssl_fake)
-        if teaching:
-            y_list = teacher.labels(frames, mask, labels, task_index, total_tasks)
+        if shared:
+            # one encoder pass, two consumers: the teacher reads the student's K/V first, then the student consumes it
+            # (which is what lets the next pass into that K/V set start)
+            enc = model.encode_clips(frames, train=True)
+            try:
+                y_list = teacher.labels(frames, mask, labels, task_index, total_tasks, encoded=enc)
+                task_losses, task_logits, other = model(frames, y_list, mask, comps, speed, train=True, single_task=None, encoded=enc)
+            finally:
+                enc.release()  # (nothing to do after the student's forward; after an error it frees the model for the next pass)
         else:
-            y_list = [labels if i == task_index else None for i in range(total_tasks)]
-        task_losses, task_logits, other = model(frames, y_list, mask, comps, speed, train=True,
-                                                single_task=None if teaching else task_index)
+            if teaching:
+                y_list = teacher.labels(frames, mask, labels, task_index, total_tasks)
+            else:
+                y_list = [labels if i == task_index else None for i in range(total_tasks)]
+            task_losses, task_logits, other = model(frames, y_list, mask, comps, speed, train=True,
+                                                    single_task=None if teaching else task_index)
         if teaching:
             loss = sum(l.mean() for l in task_losses) + sum(other[k].mean() for k in other)
         else:
