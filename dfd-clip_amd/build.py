@@ -29,10 +29,12 @@ FLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-
 # hold "yuv420_") are byte movers as well: the converter keeps six 8-byte results per lane, the fused gather align.hip's state.
 # swiglu.hip's gate kernels (every instantiation holds "swiglu_") move three elements per result and nothing else.
 # kv_gather.hip's row gathers ("kv_gather_": both forms, every instantiation) move two rows per lane and nothing else.
+# kv_frames.hip's frame movers ("kv_frames_": both forms, both load policies) move two rows per lane through two tables.
 # adapter.hip's kernels ("adapter_") are HBM-bound and the register-resident backward sits at the 128-VGPR ceiling of its 1024 threads.
 # optim.hip's EMA blend ("ema_step_kernel", both stream-policy forms) moves two loads and one or two stores per element.
 NO_SCRATCH = {"optim.hip": "ema_step_kernel", "gemm256e.hip": "gemm256e_kernel", "attention_mfma_xrow.hip": "attn_mfma_xrow_kernel", "align.hip": "align_crop_u8_kernel",
               "elastic.hip": "elastic_remap_u8_kernel", "yuv.hip": "yuv420_", "swiglu.hip": "swiglu_", "kv_gather.hip": "kv_gather_",
+              "kv_frames.hip": "kv_frames_",
               "adapter.hip": "adapter_"}
 
 
@@ -86,6 +88,7 @@ def build(force=False, verbose=False, extra_flags=()):
     headers.append(os.path.join(INCLUDE, "dfdclip_yuv.h"))
     headers.append(os.path.join(INCLUDE, "dfdclip_swiglu.h"))
     headers.append(os.path.join(INCLUDE, "dfdclip_kvgather.h"))
+    headers.append(os.path.join(INCLUDE, "dfdclip_kvframes.h"))
     headers.append(os.path.join(INCLUDE, "dfdclip_ema.h"))
     headers.append(os.path.join(INCLUDE, "dfdclip_hooks.h"))
     jobs, objs = [], []

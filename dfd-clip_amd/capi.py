@@ -236,6 +236,16 @@ KVGATHER_SIGNATURES = {
     "dfd_kv_gather_last_path": (c_int, []),
 }
 
+KVFRAMES_VEC16, KVFRAMES_ELEMENT = 1, 2  # dfd_kv_move_last_path: 16-byte accesses, or element by element
+KVFRAMES_SRC_ONCE = 1  # flags of dfd_kv_move_frames: the source is read once, its loads follow the STREAM_DECODER_KV policy bit
+
+# the K/V frame mover of the streaming path beside the ABI, in a header of its own (include/dfdclip_kvframes.h)
+KVFRAMES_SIGNATURES = {
+    "dfd_kv_move_frames": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64,
+                                   c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "dfd_kv_move_last_path": (c_int, []),
+}
+
 # the EMA-teacher update beside the ABI, in a header of its own (include/dfdclip_ema.h)
 EMA_SIGNATURES = {
     "dfd_ema_step": (c_int, [c_void_p, c_int, c_int64, c_float, c_float, c_void_p]),
@@ -309,7 +319,7 @@ def load_library(path=None):
     lib = ctypes.CDLL(path)
     for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **EXPLAIN_SIGNATURES, **AUGMENT_SIGNATURES, **ALIGN_SIGNATURES,
                                **ELASTIC_SIGNATURES, **YUV_SIGNATURES, **SWIGLU_SIGNATURES, **KVGATHER_SIGNATURES,
-                               **EMA_SIGNATURES, **HOOK_SIGNATURES}.items():
+                               **KVFRAMES_SIGNATURES, **EMA_SIGNATURES, **HOOK_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError:
@@ -618,6 +628,64 @@ def kv_gather_patches(k, v, index, pos, k_out=None, v_out=None, T=1, P=None, ind
 def kv_gather_last_path():
     """KVGATHER_VEC16 / KVGATHER_ELEMENT: the form the last `kv_gather_patches` of this thread launched (0: none, or a no-op)."""
     return load_library().dfd_kv_gather_last_path()
+
+
+def _frame_table(name, table, host, frames):
+    """Checks one side's frame table of `kv_move_frames`; returns (its length or None, the host copy or None)."""
+    if table is None:
+        return None, None
+    assert table.dtype == torch.int32 and table.dim() == 1 and table.is_contiguous(), (name, table.shape, table.dtype)
+    host = table.cpu() if host is None else torch.as_tensor(host)
+    assert host.numel() == table.numel(), (name, host.shape, table.shape)
+    if host.numel() and (int(host.min()) < 0 or int(host.max()) >= frames):
+        raise DfdError(f"kv_move_frames: {name} has an entry outside [0, {frames}) (min {int(host.min())}, max {int(host.max())})")
+    return table.numel(), host
+
+
+def kv_move_frames(k, v, k_out, v_out, src_frame=None, dst_frame=None, src_once=False, src_host=None, dst_host=None):
+    """k_out[l, dst_frame[i], p] = k[l, src_frame[i], p], the same for v (include/dfdclip_kvframes.h): whole frames of K and V of
+    every tapped layer in one launch, bits copied.
+
+    k, v: two views of one layout [L, src_frames, P, D], bf16 or f32, unit column stride and any other strides (the views
+    `extract_kv(in_place=)` returns, or a dense store).  k_out, v_out: the same for the destination, [L, dst_frames, P, D].
+    src_frame / dst_frame: device int32 [n], or None for the identity (then n is the other table's length, or the frame
+    count both sides share).  src_once: the source is read once (an ingest), so its loads follow the STREAM_DECODER_KV bit.
+    Raises before the launch when a table has an entry outside its side, or dst_frame names a frame twice (the kernel
+    would clamp the one and race on the other): `src_host` / `dst_host` are the host copies to look at — without them the
+    device tables are copied back, which synchronises.  Returns (k_out, v_out)."""
+    _dev(k, v, k_out, v_out, src_frame, dst_frame)
+    assert k.dtype == v.dtype == k_out.dtype == v_out.dtype and k.dtype in _DTYPE, (k.dtype, v.dtype, k_out.dtype, v_out.dtype)
+    assert k.dim() == 4 and k.shape == v.shape and k.stride() == v.stride(), "k and v are two views of one layout"
+    assert k_out.dim() == 4 and k_out.shape == v_out.shape and k_out.stride() == v_out.stride(), "k_out and v_out are two views of one layout"
+    L, src_frames, P, D = k.shape
+    assert (k_out.shape[0], k_out.shape[2], k_out.shape[3]) == (L, P, D), (k.shape, k_out.shape)
+    dst_frames = k_out.shape[1]
+    assert (k.stride(3) == 1 and k_out.stride(3) == 1) or D <= 1, "rows are dense: unit column stride"
+    n_src, _ = _frame_table("src_frame", src_frame, src_host, src_frames)
+    n_dst, host = _frame_table("dst_frame", dst_frame, dst_host, dst_frames)
+    if n_src is not None and n_dst is not None:
+        assert n_src == n_dst, (n_src, n_dst)
+    n = n_src if n_src is not None else n_dst
+    if n is None:
+        assert src_frames == dst_frames, "without a table both sides hold the same frames"
+        n = src_frames
+    if (src_frame is None and n > src_frames) or (dst_frame is None and n > dst_frames):
+        raise DfdError(f"kv_move_frames: {n} frames under an identity table exceed that side (src {src_frames}, dst {dst_frames})")
+    if host is not None and len(set(host.tolist())) != host.numel():
+        raise DfdError("kv_move_frames: dst_frame names a frame twice: two moves into one frame would race")
+    if L == 0 or n == 0 or P == 0 or D == 0:
+        return k_out, v_out  # (an empty tensor has no address to hand over; the ABI's no-op)
+    # (a dimension of size 1 may carry any stride in torch; the ABI wants stride_patch >= D whatever the sizes)
+    _check(load_library().dfd_kv_move_frames(_ptr(k), _ptr(v), _ptr(k_out), _ptr(v_out), _DTYPE[k.dtype], k.stride(0), k.stride(1),
+                                             max(k.stride(2), D), k_out.stride(0), k_out.stride(1), max(k_out.stride(2), D),
+                                             _ptr(src_frame), _ptr(dst_frame), L, n, src_frames, dst_frames, P, D,
+                                             KVFRAMES_SRC_ONCE if src_once else 0, _stream()), "dfd_kv_move_frames")
+    return k_out, v_out
+
+
+def kv_move_last_path():
+    """KVFRAMES_VEC16 / KVFRAMES_ELEMENT: the form the last `kv_move_frames` of this thread launched (0: none, or a no-op)."""
+    return load_library().dfd_kv_move_last_path()
 
 
 def profile_gemm(epilogue=None):

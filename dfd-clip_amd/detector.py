@@ -933,6 +933,25 @@ class Detector(RuntimeStateMixin, nn.Module):
             raise ValueError(f"{a.shape[-1]} patches are not a square grid")
         return a.view(*a.shape[:3], g, g)
 
+    def push_frames(self, store, frames, valid=None):
+        """Frames through the tower ONCE, into a `stream.FrameStore` of this model: frames f32 [N,3,R,R] or uint8 [N,3,H,W]
+        on the device (what the encoder takes), N at most the store's `encode_chunk`; `valid` [N] bool (default all) is the
+        frame mask windows will carry.  One tower pass writes q|k|v in place into the store's private staging buffer, one
+        `dfd_kv_move_frames` launch moves the raw K/V rows (no positional embedding, before any adapter) into the ring slots,
+        all on the current stream.  It does not go through `_encode`: the persistent K/V sets, an open `encode_clips` handle
+        and the encoder graph are not touched.  Returns the range of absolute frame indices the frames got."""
+        from . import stream
+        return stream.push_frames(self, store, frames, valid)
+
+    def predict_windows(self, store, table, with_video_features=False):
+        """`predict` for windows of stored frames: table [W, num_frames] absolute frame indices (`stream.window_table`); a
+        frame that is evicted or not pushed yet raises by its index.  One `dfd_kv_move_frames` launch gathers the windows'
+        raw rows into the store's dense [L, W*T, P, D] buffer, then exactly what `predict` does after the tower: the adapter
+        where there is one, the decoder with this model's positional embedding, the stored `valid` flags as the mask.
+        No-grad inference in eval mode only.  Returns (task_logits, features) like `predict`."""
+        from . import stream
+        return stream.predict_windows(self, store, table, with_video_features)
+
     def _build_adapter(self, config, num_frames):
         """`adapter.type` none / normal (fresh) / pretrain (parameters from a checkpoint of a whole Detector, optionally
         frozen): reference `src/models.py:454-478`.  Checkpoints are read with `weights_only=True`."""

@@ -27,7 +27,8 @@ code, so that a reference user finds the same step semantics on top of `Detector
                   the dummy [0, 1] pair the reference appends before computing.
   infer_raw_video `pipeline.py:114-182` + `:328-351`: decoded frames (RGB tensors, or the decoder's 4:2:0 surfaces as a
                   `yuv.Yuv420`) + landmarks -> face-aligned crops on the device (`align.FaceAligner`) -> clips of num_frames, ragged tail dropped -> predict in chunks -> softmax ->
-                  mean over clips -> probability of class 1.
+                  mean over clips -> probability of class 1.  `hop=`: overlapping windows over a per-frame K/V store
+                  (`stream.StreamingVerdict`, exported here too) instead of disjoint clips.
 """
 import copy
 import logging
@@ -37,6 +38,7 @@ from torch.optim.lr_scheduler import OneCycleLR
 
 from . import capi
 from . import dist as ddist
+from .stream import StreamingVerdict
 
 _log = logging.getLogger(__name__)
 
@@ -369,7 +371,7 @@ def infer_videos(model, videos, batch_size=30, modality="video", task_index=0, d
 
 @torch.no_grad()
 def infer_raw_video(model, frames, landmarks, aligner, batch_size=16, task_index=0, layout="hwc", swap_rb=False, with_logits=False,
-                    matrix=None):
+                    matrix=None, hop=None, tail="drop", encode_chunk=None):
     """One decoded video to a verdict, as `pipeline.get_result` does after its file handling (`pipeline.py:328-351`), with
     the face alignment it reads from a pre-cropped file done here on the device (`align.FaceAligner`).
 
@@ -380,7 +382,14 @@ def infer_raw_video(model, frames, landmarks, aligner, batch_size=16, task_index
     consecutive frames, a ragged last clip is dropped (`pipeline.py:334-336`), `predict` runs on uint8 clips in chunks of
     `batch_size` with `plan.valid` (frames with a face) as the mask, and the softmax is averaged over clips.
     Returns (probability of class 1, per-clip probabilities [clips, classes]) on the host; `with_logits` appends the
-    per-clip logits."""
+    per-clip logits.
+
+    `hop` (an integer; None is the path above, untouched): overlapping windows of `model.num_frames` frames every `hop`
+    frames, through a `stream.StreamingVerdict` fed with the crops in passes of `encode_chunk` frames (default
+    `batch_size * num_frames`, the tower pass of the path above): every frame goes through the tower once, the K/V ring
+    holds `num_frames + encode_chunk` frames whatever the length of the video, and "clips" above reads "windows".
+    `tail` is `stream.window_table`'s: "drop" as above, "last" adds the window that ends on the last frame.  Under
+    `precision="fp8"` the verdict depends on `encode_chunk` (`stream`'s note)."""
     model.eval()
     plan = aligner.plan(landmarks)
     from .yuv import Yuv420
@@ -396,6 +405,13 @@ def infer_raw_video(model, frames, landmarks, aligner, batch_size=16, task_index
     n = crops.shape[0] // T
     if n == 0:
         raise ValueError(f"{crops.shape[0]} frames do not fill one clip of {T}")
+    if hop is not None:
+        chunk = int(encode_chunk) if encode_chunk is not None else batch_size * T
+        sv = StreamingVerdict(model, hop, encode_chunk=chunk, batch_size=batch_size, task_index=task_index, tail=tail)
+        for i in range(0, crops.shape[0], chunk):
+            sv.push(crops[i:i + chunk], plan.valid[i:i + chunk])
+        sv.flush()
+        return sv.result(with_logits=with_logits)
     clips = crops[:n * T].view(n, T, *crops.shape[1:])
     mask = torch.from_numpy(plan.valid[:n * T].copy()).view(n, T).to(crops.device)
     logits = []
