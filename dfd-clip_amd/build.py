@@ -89,6 +89,7 @@ def build(force=False, verbose=False, extra_flags=()):
     headers.append(os.path.join(INCLUDE, "dfdclip_swiglu.h"))
     headers.append(os.path.join(INCLUDE, "dfdclip_kvgather.h"))
     headers.append(os.path.join(INCLUDE, "dfdclip_kvframes.h"))
+    headers.append(os.path.join(INCLUDE, "dfdclip_kvtable.h"))
     headers.append(os.path.join(INCLUDE, "dfdclip_ema.h"))
     headers.append(os.path.join(INCLUDE, "dfdclip_hooks.h"))
     jobs, objs = [], []

@@ -246,6 +246,15 @@ KVFRAMES_SIGNATURES = {
     "dfd_kv_move_last_path": (c_int, []),
 }
 
+# decoder attention over a frame store, read in place through a slot table, beside the ABI, in a header of its own
+# (include/dfdclip_kvtable.h): the arguments of dfd_decoder_attn_fwd / dfd_decoder_attn_map, then frame_table and store_frames
+KVTABLE_SIGNATURES = {
+    "dfd_decoder_attn_fwd_frames": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "dfd_decoder_attn_map_frames": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                            c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+}
+
 # the EMA-teacher update beside the ABI, in a header of its own (include/dfdclip_ema.h)
 EMA_SIGNATURES = {
     "dfd_ema_step": (c_int, [c_void_p, c_int, c_int64, c_float, c_float, c_void_p]),
@@ -319,7 +328,7 @@ def load_library(path=None):
     lib = ctypes.CDLL(path)
     for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **EXPLAIN_SIGNATURES, **AUGMENT_SIGNATURES, **ALIGN_SIGNATURES,
                                **ELASTIC_SIGNATURES, **YUV_SIGNATURES, **SWIGLU_SIGNATURES, **KVGATHER_SIGNATURES,
-                               **KVFRAMES_SIGNATURES, **EMA_SIGNATURES, **HOOK_SIGNATURES}.items():
+                               **KVFRAMES_SIGNATURES, **KVTABLE_SIGNATURES, **EMA_SIGNATURES, **HOOK_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError:
@@ -1011,6 +1020,62 @@ def decoder_attn_map(q, k, frame_mask, stats, aff, B, T, patches, heads, d=64, e
     _check(load_library().dfd_decoder_attn_map(_ptr(q), _ptr(k), _DTYPE[k.dtype], lay, _ptr(frame_mask), _ptr(stats), _ptr(ext_weights),
                                                _ptr(aff), _ptr(branches), B, T, patches, heads, d, _stream()),
            "dfd_decoder_attn_map")
+    return aff
+
+
+def _store_layout(who, k, v, table, table_host, pos, B, T, patches, D):
+    """One layer of a frame store [C, patches, D] (contiguous, or a strided view with unit column stride) and the slot
+    table of `decoder_attn_fwd_frames` / `decoder_attn_map_frames`, checked: -> (layout, keep-alive, store_frames).  Raises
+    before any launch when the table has an entry outside [0, C) (the kernel would clamp it): `table_host` is the host copy to
+    look at — without it the device table is copied back, which synchronises."""
+    assert k.dim() == 3 and k.shape[1:] == (patches, D) and (k.stride(2) == 1 or D <= 1), f"{who}: a store layer is [C, {patches}, {D}] with unit column stride"
+    if v is not None:
+        assert v.dtype == k.dtype and v.shape == k.shape and v.stride() == k.stride(), f"{who}: k and v are two views of one layout"
+    C = k.shape[0]
+    assert table.dtype == torch.int32 and table.dim() == 1 and table.is_contiguous() and table.numel() == B * T, (who, table.shape, table.dtype)
+    host = table.cpu() if table_host is None else torch.as_tensor(table_host)
+    assert host.numel() == table.numel(), (who, host.shape, table.shape)
+    if host.numel() and (int(host.min()) < 0 or int(host.max()) >= C):
+        raise DfdError(f"{who}: the frame table has an entry outside [0, {C}) (min {int(host.min())}, max {int(host.max())})")
+    if pos is not None:
+        assert pos.dtype == torch.float32 and pos.is_contiguous() and pos.shape == (T, D) and pos.device == k.device
+    # (a dimension of size 1 may carry any stride in torch; the ABI wants row_stride >= D and frame_stride > 0 whatever the sizes)
+    lay = KvLayoutDesc(max(k.stride(1), D), max(k.stride(0), 1), pos.data_ptr() if pos is not None else None)
+    return ctypes.byref(lay), lay, C
+
+
+def decoder_attn_fwd_frames(q, k, v, table, frame_mask, mix, stats, workspace, splits, B, T, patches, heads, d=64, mix_softmax=None,
+                            ext_weights=None, pos=None, table_host=None):
+    """`decoder_attn_fwd` with the keys and values of clip b's frame tf read at frame `table[b*T + tf]` of the store layer
+    k, v [C, patches, D] (include/dfdclip_kvtable.h): no dense copy of the windows' frames.  `table`: device int32 [B*T];
+    `frame_mask` [B, T] and `pos` [T, D] stay indexed by the clip's own frame."""
+    _dev(q, k, v, table, frame_mask, mix, stats, workspace, mix_softmax, ext_weights)
+    assert q.dtype == torch.float32 and q.is_contiguous()
+    assert frame_mask.dtype == torch.uint8 and frame_mask.is_contiguous()
+    assert ext_weights is None or (ext_weights.is_contiguous() and ext_weights.numel() == B * heads * T * patches)
+    lay, _keep, C = _store_layout("decoder_attn_fwd_frames", k, v, table, table_host, pos, B, T, patches, heads * d)
+    _check(load_library().dfd_decoder_attn_fwd_frames(_ptr(q), _ptr(k), _ptr(v), _DTYPE[k.dtype], lay, _ptr(frame_mask), _ptr(ext_weights),
+                                                      _ptr(mix), _ptr(mix_softmax), _ptr(stats), _ptr(workspace), splits, B, T, patches,
+                                                      heads, d, _ptr(table), C, _stream()),
+           "dfd_decoder_attn_fwd_frames")
+    return mix
+
+
+def decoder_attn_map_frames(q, k, table, frame_mask, stats, aff, B, T, patches, heads, d=64, ext_weights=None, branches=None, pos=None,
+                            table_host=None):
+    """`decoder_attn_map` over the store layer k [C, patches, D] and the slot table that `decoder_attn_fwd_frames` read."""
+    _dev(q, k, table, frame_mask, stats, aff, ext_weights, branches)
+    assert q.dtype == torch.float32 and q.is_contiguous()
+    assert frame_mask.dtype == torch.uint8 and frame_mask.is_contiguous()
+    n = B * heads * T * patches
+    assert aff.dtype == torch.float32 and aff.is_contiguous() and aff.numel() == n
+    assert stats is None or (stats.dtype == torch.float32 and stats.is_contiguous() and stats.numel() == B * heads * 2)
+    assert ext_weights is None or (ext_weights.dtype == torch.float32 and ext_weights.is_contiguous() and ext_weights.numel() == n)
+    assert branches is None or (branches.dtype == torch.float32 and branches.is_contiguous() and branches.numel() == 2 * n)
+    lay, _keep, C = _store_layout("decoder_attn_map_frames", k, None, table, table_host, pos, B, T, patches, heads * d)
+    _check(load_library().dfd_decoder_attn_map_frames(_ptr(q), _ptr(k), _DTYPE[k.dtype], lay, _ptr(frame_mask), _ptr(stats), _ptr(ext_weights),
+                                                      _ptr(aff), _ptr(branches), B, T, patches, heads, d, _ptr(table), C, _stream()),
+           "dfd_decoder_attn_map_frames")
     return aff
 
 

@@ -11,23 +11,29 @@
 //   softmax state (max, sum, acc_s[8]) and the CoDA accumulator acc_c[8] for its channels.
 //   Workgroups split S; partial states are merged by decoder_attn_combine_kernel, which also
 //   emits (max, sumexp) per (clip, head) for the backward pass.
+// dfd_decoder_attn_fwd_frames (include/dfdclip_kvtable.h) — the same kernels with TAB: the frames of a clip are read out of
+//   a frame store through a slot table, with no copy in between.
 // dfd_linear_rows — y[B,N] = x[B,K]·W[N,K]ᵀ + b: one wave per output column streams the weight
 //   row once per 8 clips; x stays L1/L2 resident.
 // dfd_head_fwd — ln_post + projection + 5·z/(‖z‖+1e-10).
 #include "dropout.hpp"
 #include "decoder_common.hpp"
+#include "../../include/dfdclip_kvtable.h"
 
 namespace {
 
-template <typename T, int MAXT, bool POS, bool NT>
+// TAB: k / v are the store's layer bases and frame tf of clip b is frame frame_table[b*T + tf] of the store (clamped to
+// [0, store_frames)); without TAB the two arguments are not read and the kernel is the one it was before they existed
+template <typename T, int MAXT, bool POS, bool NT, bool TAB>
 __global__ __launch_bounds__(MAXT, (MAXT <= 512 ? (POS ? 2 : 3) : 4)) void decoder_attn_partial_kernel(const float* __restrict__ q, const T* __restrict__ k,
                                                                     const T* __restrict__ v,
                                                                     const uint8_t* __restrict__ frame_mask,
                                                                     const float* __restrict__ ext_w,
                                                                     float* __restrict__ ws, int splits, int T_frames,
                                                                     int patches, int heads, int R, KvLayout lay,
-                                                                    FastDiv div_patches) {
-  extern __shared__ float red[];  // [R][tpr][18], then (POS) the positional embedding of this block's frames
+                                                                    FastDiv div_patches,
+                                                                    const int32_t* __restrict__ frame_table, int store_frames) {
+  extern __shared__ float red[];  // [R][tpr][18], then (POS) the positional embedding of this block's frames, then (TAB) T slots
   const HeadLanes ln(heads);
   const int tpr = ln.tpr, rs = ln.rs, tr = ln.tr, hd = ln.hd, sub = ln.sub;
   const int b = blockIdx.y, split = blockIdx.x;
@@ -37,6 +43,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 512 ? (POS ? 2 : 3) : 4)) void decod
   const int s_begin = split * per;
   const int s_end = min(S, s_begin + per);
   float* const posl = red + (size_t)blockDim.x * 18;
+  const int* const slots = stage_slots<TAB, POS>(posl, frame_table, store_frames, b, T_frames, s_begin, s_end, S, D, div_patches);
   const int f0 = stage_pos<POS>(posl, lay.pos, s_begin, s_end, S, D, div_patches);
 
   float qs[8], qc[8];
@@ -45,16 +52,17 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 512 ? (POS ? 2 : 3) : 4)) void decod
 #pragma unroll
   for (int e = 0; e < 8; ++e) { as[e] = 0.f; ac[e] = 0.f; }
 
-  const T* kb = ln.channels(k + (int64_t)b * T_frames * lay.frame_stride);
-  const T* vb = ln.channels(v + (int64_t)b * T_frames * lay.frame_stride);
-  const KeySpan sp{s_end, S, D, f0, patches, R, lay, div_patches, frame_mask + (int64_t)b * T_frames, ln.channels(posl)};
+  const int64_t clip0 = TAB ? 0 : (int64_t)b * T_frames * lay.frame_stride;
+  const T* kb = ln.channels(k + clip0);
+  const T* vb = ln.channels(v + clip0);
+  const KeySpan sp{s_end, S, D, f0, patches, R, lay, div_patches, frame_mask + (int64_t)b * T_frames, ln.channels(posl), slots};
   // The front (key_trip) leaves this lane with the sums of its own row of the trip; the row weights then travel back to
   // the group for the V accumulation.  The softmax is rescaled once per trip.
   float l_own = 0.f;  // softmax weights of the rows this lane finished; summed over the group at the end
   for (int s0 = s_begin + rs; s0 < s_end; s0 += UN * R) {
     Raw8<T> vr[UN];
     int po[UN];  // LDS offset of the row's frame in the staged positional embeddings
-    const KeyRow me = key_trip<T, POS, NT, true>(sp, ln, qs, qc, kb, vb, s0, vr, po);
+    const KeyRow me = key_trip<T, POS, NT, true, TAB>(sp, ln, qs, qc, kb, vb, s0, vr, po);
     const bool ok = me.ok;
     float p;
     if (ext_w != nullptr) {
@@ -433,45 +441,79 @@ extern "C" size_t dfd_decoder_attn_workspace(int B, int heads, int d, int splits
   return (size_t)B * splits * heads * PART * sizeof(float);
 }
 
-extern "C" int dfd_decoder_attn_fwd(const float* q, const void* k, const void* v, int kv_dtype, const dfd_kv_layout_t* layout,
-                                    const uint8_t* frame_mask, const float* ext_weights, float* mix, float* mix_softmax,
-                                    float* stats, void* workspace, int splits, int B, int T, int patches, int heads, int d,
-                                    void* stream) {
-  if (int rc = check_decoder_attn("dfd_decoder_attn_fwd", q && k && v && frame_mask && mix && stats && workspace, {k, v, q}, kv_dtype,
-                                  layout, B, T, patches, heads, d))
+namespace {
+
+// dfd_decoder_attn_fwd (frame_table == nullptr) and dfd_decoder_attn_fwd_frames: one check, one plan, the TAB flag apart
+int decoder_attn_fwd(const char* who, const float* q, const void* k, const void* v, int kv_dtype, const dfd_kv_layout_t* layout,
+                     const uint8_t* frame_mask, const float* ext_weights, float* mix, float* mix_softmax, float* stats,
+                     void* workspace, int splits, int B, int T, int patches, int heads, int d, const int32_t* frame_table,
+                     int store_frames, void* stream) {
+  const bool tab = frame_table != nullptr;
+  if (int rc = check_decoder_attn(who, q && k && v && frame_mask && mix && stats && workspace, {k, v, q}, kv_dtype, layout, B, T,
+                                  patches, heads, d))
     return rc;
-  DFD_REQUIRE(splits > 0 && splits <= 4096, "dfd_decoder_attn_fwd: splits=%d", splits);
+  DFD_REQUIRE(splits > 0 && splits <= 4096, "%s: splits=%d", who, splits);
   // decoder_attn_combine_kernel keeps one rescale weight per (head, split) in LDS beside its two static rows; what no
   // launch can get is refused here, before the partial kernel is launched, rather than by the combine launch
   const size_t combine_lds = (size_t)heads * splits * sizeof(float), combine_static = 2 * 16 * sizeof(float);
   DFD_REQUIRE(combine_lds + combine_static <= 160 * 1024,
-              "dfd_decoder_attn_fwd: splits=%d with heads=%d needs %zu B of LDS to merge (heads*splits <= 40928)", splits, heads,
-              combine_lds);
+              "%s: splits=%d with heads=%d needs %zu B of LDS to merge (heads*splits <= 40928)", who, splits, heads, combine_lds);
   if (B == 0) return DFD_OK;
   const KvLayout lay = dfd_kv_layout(layout, patches, heads * HD);
   const FastDiv divp = FastDiv::make((uint32_t)patches);
   const AttnBlock blk = decoder_attn_block(heads);
   const int S_ = T * patches, per_ = (S_ + splits - 1) / splits;
   const int span = lay.pos ? (per_ + patches - 2) / patches + 1 : 0;  // frames a block's rows can touch
-  const size_t lds = (size_t)blk.threads * 18 * sizeof(float) + (size_t)(span < T ? span : T) * heads * HD * sizeof(float);
-  DFD_REQUIRE(lds <= 160 * 1024, "dfd_decoder_attn_fwd: %zu B of LDS (use more splits)", lds);
+  const size_t lds = (size_t)blk.threads * 18 * sizeof(float) + (size_t)(span < T ? span : T) * heads * HD * sizeof(float) +
+                     (tab ? (size_t)T * sizeof(int) : 0);  // the clip's staged slots
+  DFD_REQUIRE(lds <= 160 * 1024, "%s: %zu B of LDS (use more splits)", who, lds);
   hipStream_t st = static_cast<hipStream_t>(stream);
   float* ws = static_cast<float*>(workspace);
-  const int rc = decoder_attn_dispatch(
-      kv_dtype, blk.threads, lay.pos != nullptr, dfd_stream_on(DFD_STREAM_DECODER_KV), [&](auto kt, auto mt, auto ps, auto nt) {
-        using KT = typename decltype(kt)::type;
-        return launch_kernel("dfd_decoder_attn_fwd(partial)",
-                             decoder_attn_partial_kernel<KT, decltype(mt)::value, decltype(ps)::value, decltype(nt)::value>,
-                             Launch{dim3(splits, B), dim3(blk.threads), lds, st}, q, k, v, frame_mask, ext_weights, ws, splits, T,
-                             patches, heads, blk.R, lay, divp);
-      });
+  const Launch launch{dim3(splits, B), dim3(blk.threads), lds, st};
+  // the tabled loads are plain whatever the policy says: a stored frame is read by every window that names it
+  const int rc =
+      tab ? decoder_attn_dispatch(kv_dtype, blk.threads, lay.pos != nullptr, false,
+                                  [&](auto kt, auto mt, auto ps, auto) {
+                                    using KT = typename decltype(kt)::type;
+                                    return launch_kernel("dfd_decoder_attn_fwd_frames(partial)",
+                                                         decoder_attn_partial_kernel<KT, decltype(mt)::value, decltype(ps)::value, false, true>,
+                                                         launch, q, k, v, frame_mask, ext_weights, ws, splits, T, patches, heads, blk.R, lay,
+                                                         divp, frame_table, store_frames);
+                                  })
+          : decoder_attn_dispatch(kv_dtype, blk.threads, lay.pos != nullptr, dfd_stream_on(DFD_STREAM_DECODER_KV),
+                                  [&](auto kt, auto mt, auto ps, auto nt) {
+                                    using KT = typename decltype(kt)::type;
+                                    return launch_kernel(
+                                        "dfd_decoder_attn_fwd(partial)",
+                                        decoder_attn_partial_kernel<KT, decltype(mt)::value, decltype(ps)::value, decltype(nt)::value, false>,
+                                        launch, q, k, v, frame_mask, ext_weights, ws, splits, T, patches, heads, blk.R, lay, divp, nullptr, 0);
+                                  });
   if (rc != DFD_OK) return rc;
   // one thread per channel of up to 16 heads; wider towers (ViT-g/14: 24 heads) merge their heads in equal groups on grid.y
   int hpb = heads < 16 ? heads : 16;
   while (heads % hpb != 0) --hpb;
-  return launch_kernel("dfd_decoder_attn_fwd(combine)", decoder_attn_combine_kernel,
+  return launch_kernel(tab ? "dfd_decoder_attn_fwd_frames(combine)" : "dfd_decoder_attn_fwd(combine)", decoder_attn_combine_kernel,
                        Launch{dim3(B, heads / hpb), dim3(hpb * HD), (size_t)hpb * splits * sizeof(float), st, combine_static}, ws, mix,
                        mix_softmax, stats, splits, heads);
+}
+
+}  // namespace
+
+extern "C" int dfd_decoder_attn_fwd(const float* q, const void* k, const void* v, int kv_dtype, const dfd_kv_layout_t* layout,
+                                    const uint8_t* frame_mask, const float* ext_weights, float* mix, float* mix_softmax,
+                                    float* stats, void* workspace, int splits, int B, int T, int patches, int heads, int d,
+                                    void* stream) {
+  return decoder_attn_fwd("dfd_decoder_attn_fwd", q, k, v, kv_dtype, layout, frame_mask, ext_weights, mix, mix_softmax, stats, workspace,
+                          splits, B, T, patches, heads, d, nullptr, 0, stream);
+}
+
+extern "C" int dfd_decoder_attn_fwd_frames(const float* q, const void* k, const void* v, int kv_dtype, const dfd_kv_layout_t* layout,
+                                           const uint8_t* frame_mask, const float* ext_weights, float* mix, float* mix_softmax,
+                                           float* stats, void* workspace, int splits, int B, int T, int patches, int heads, int d,
+                                           const int32_t* frame_table, int store_frames, void* stream) {
+  if (int rc = check_frame_table("dfd_decoder_attn_fwd_frames", frame_table, store_frames)) return rc;
+  return decoder_attn_fwd("dfd_decoder_attn_fwd_frames", q, k, v, kv_dtype, layout, frame_mask, ext_weights, mix, mix_softmax, stats,
+                          workspace, splits, B, T, patches, heads, d, frame_table, store_frames, stream);
 }
 
 // shared by the attn_mode entry points (declared in decoder_common.hpp for decoder_bwd.hip)

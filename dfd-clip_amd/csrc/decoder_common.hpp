@@ -4,7 +4,8 @@
 // of the positional embedding, and the eight-row trip that leaves each lane with the three sums of its own key row.  Host:
 // the argument check of the five entry points, the block-size rule, the launch helper and the dispatch from (key type,
 // block size, POS, NT) to an instantiation.  A new K/V addressing mode is an edit of kv_row_offset / key_trip, of
-// check_decoder_attn and of the backward's walk over its one frame.
+// check_decoder_attn and of the backward's walk over its one frame.  TAB is one: the forward and the map read the frames
+// of a clip out of a frame store through a slot table (include/dfdclip_kvtable.h); the backward does not.
 #pragma once
 #include <initializer_list>
 #include <type_traits>
@@ -135,10 +136,16 @@ __device__ __forceinline__ void load_query(const float* q, int b, int heads, con
   }
 }
 
-// row s of a clip = patch s % patches of its frame tf = s / patches (KvLayout: dense export or the qkv activation in place)
-__device__ __forceinline__ int64_t kv_row_offset(int s, int patches, const KvLayout& lay, const FastDiv& div_patches, int& tf) {
+// row s of a clip = patch s % patches of its frame tf = s / patches (KvLayout: dense export or the qkv activation in place).
+// TAB: the frame is frame slots[tf] of a store, not frame tf of the clip (`slots`: the clip's T entries as stage_slots left
+// them, clamped); the offset is then relative to the store's base, and the product is formed in 64 bits like the other.
+template <bool TAB = false>
+__device__ __forceinline__ int64_t kv_row_offset(int s, int patches, const KvLayout& lay, const FastDiv& div_patches, int& tf,
+                                                 const int* slots = nullptr) {
   tf = (int)div_patches.div((uint32_t)s);
-  return (int64_t)tf * lay.frame_stride + (int64_t)(s - tf * patches) * lay.row_stride;
+  int f = tf;
+  if constexpr (TAB) f = slots[tf];
+  return (int64_t)f * lay.frame_stride + (int64_t)(s - tf * patches) * lay.row_stride;
 }
 
 // POS: the rows [s_begin, s_end) of a workgroup lie in frames f0 .. f1 of the clip; their positional embeddings are staged
@@ -159,6 +166,34 @@ __device__ __forceinline__ int stage_pos(float* posl, const float* pos, int s_be
   return f0;
 }
 
+// TAB: the T slots of clip b (frame_table[b*T .. b*T + T)) are staged once per workgroup in the dynamic LDS behind the
+// positional rows that stage_pos puts at `posl`, each clamped to [0, store_frames) on the way (the rule of kv_frames.hip:
+// no address is formed from an entry as given).  Staged, not read per row through the cache, by the compiler's report
+// (profiles/decoder_table_resources.txt): staged, every tabled instantiation has the VGPRs and the occupancy of its untabled
+// twin, one ds_read_b32 per row and no further barrier with POS; read per row (a global load and a clamp in front of every
+// K / V load) the forward's 512-thread bf16 forms, the ones ViT-B/16 runs, take 6 to 7 VGPRs more and the map up to 11.
+// Call it BEFORE stage_pos: with POS that call's barrier covers the slots too; without POS the barrier is here.  Returns
+// the staged slots (nullptr without TAB: nothing is staged or read).
+template <bool TAB, bool POS>
+__device__ __forceinline__ const int* stage_slots(float* posl, const int32_t* frame_table, int store_frames, int b, int T_frames,
+                                                  int s_begin, int s_end, int S, int D, const FastDiv& div_patches) {
+  if constexpr (!TAB) {
+    return nullptr;
+  } else {
+    int* sl = reinterpret_cast<int*>(posl);
+    if constexpr (POS) {  // behind the frames f0 .. f1 that stage_pos stages (the same two divisions)
+      const int f0 = (int)div_patches.div((uint32_t)min(s_begin, S - 1));
+      const int last = max(s_end, s_begin + 1) - 1;
+      const int f1 = (int)div_patches.div((uint32_t)(last < S ? last : S - 1));
+      sl += (f1 - f0 + 1) * D;
+    }
+    const int32_t* tb = frame_table + (int64_t)b * T_frames;
+    for (int i = threadIdx.x; i < T_frames; i += blockDim.x) sl[i] = min(max(tb[i], 0), store_frames - 1);
+    if constexpr (!POS) __syncthreads();
+    return sl;
+  }
+}
+
 // the keys of one clip up to s_end, as a workgroup walks them
 struct KeySpan {
   int s_end, S, D, f0, patches, R;
@@ -166,6 +201,7 @@ struct KeySpan {
   FastDiv div_patches;
   const uint8_t* mb;  // the clip's frame mask
   const float* pb;    // POS: the lane's channels of frame f0 in the staged positional embedding
+  const int* slots;   // TAB: the clip's staged frame slots (stage_slots); the mask and `pb` stay indexed by the clip's frame
 };
 // the lane's own row of a trip: its three sums over the head, its index, and whether it is a key (in range, frame valid)
 struct KeyRow {
@@ -178,8 +214,9 @@ struct KeyRow {
 // use (the loop is a latency chain otherwise).  Every lane forms its 8-channel share of the three dot products of all eight
 // rows; a reduce-scatter over the group leaves lane j with the totals of row j, so the row's transcendentals (exp, tanh,
 // sigmoid: the VALU bulk of these kernels) run ONCE per row instead of once per lane.  kb / vb: the lane's channels of
-// the clip's first row; WITH_V keeps the value rows in vr for the caller; po[u]: offset of row u's frame behind sp.pb.
-template <typename T, bool POS, bool NT, bool WITH_V>
+// the clip's first row (TAB: of the store's first row); WITH_V keeps the value rows in vr for the caller; po[u]: offset of
+// row u's frame behind sp.pb.
+template <typename T, bool POS, bool NT, bool WITH_V, bool TAB = false>
 __device__ __forceinline__ KeyRow key_trip(const KeySpan& sp, const HeadLanes& ln, const float (&qs)[8], const float (&qc)[8],
                                            const T* kb, const T* vb, int s0, Raw8<T> (&vr)[WITH_V ? UN : 1], int (&po)[UN]) {
   Raw8<T> kr[UN];
@@ -187,7 +224,7 @@ __device__ __forceinline__ KeyRow key_trip(const KeySpan& sp, const HeadLanes& l
   for (int u = 0; u < UN; ++u) {
     int tf;
     const int s = min(s0 + u * sp.R, sp.s_end - 1);  // clamp: rows past the end are loaded but not used
-    const int64_t off = kv_row_offset(s, sp.patches, sp.lay, sp.div_patches, tf);
+    const int64_t off = kv_row_offset<TAB>(s, sp.patches, sp.lay, sp.div_patches, tf, sp.slots);
     kr[u].template load<NT>(kb + off);
     if constexpr (WITH_V) vr[u].template load<NT>(vb + off);
     po[u] = (tf - sp.f0) * sp.D;
@@ -241,6 +278,13 @@ inline int check_decoder_attn(const char* who, bool given, std::initializer_list
               "%s: key/value layout: row stride %lld, frame stride %lld (elements; rows must stay 16-byte aligned)", who,
               (long long)l->row_stride, (long long)l->frame_stride);
   DFD_REQUIRE(!l->pos || dfd_aligned16(l->pos), "%s: the positional embedding must be 16-byte aligned", who);
+  return DFD_OK;
+}
+
+// What the two frame-table entry points (include/dfdclip_kvtable.h) refuse on top of check_decoder_attn.
+inline int check_frame_table(const char* who, const int32_t* frame_table, int store_frames) {
+  DFD_REQUIRE(frame_table != nullptr, "%s: null frame table", who);
+  DFD_REQUIRE(store_frames > 0, "%s: store_frames=%d: the store needs at least one frame", who, store_frames);
   return DFD_OK;
 }
 

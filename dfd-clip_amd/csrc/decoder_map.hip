@@ -8,8 +8,11 @@
 //   puts its two weights into LDS ([2][heads][per]), and after one barrier the workgroup writes each head's run of `per`
 //   contiguous floats with 16-byte stores (dword stores only before the first and after the last 16-byte boundary of the
 //   run: S need not be a multiple of 4, so runs start at any dword).
+// dfd_decoder_attn_map_frames (include/dfdclip_kvtable.h) — the same kernel with TAB: K is a frame store read through the
+//   slot table that dfd_decoder_attn_fwd_frames read it through.
 #include "decoder_common.hpp"
 #include "../../include/dfdclip_explain.h"
+#include "../../include/dfdclip_kvtable.h"
 
 namespace {
 
@@ -31,14 +34,15 @@ __device__ __forceinline__ void store_runs(float* dst0, int64_t S, int heads, in
   }
 }
 
-template <typename T, int MAXT, bool POS>
+template <typename T, int MAXT, bool POS, bool TAB>
 __global__ __launch_bounds__(MAXT) void decoder_attn_map_kernel(const float* __restrict__ q, const T* __restrict__ k,
                                                                const uint8_t* __restrict__ frame_mask,
                                                                const float* __restrict__ stats, const float* __restrict__ ext_w,
                                                                float* __restrict__ aff, float* __restrict__ branches,
                                                                int64_t branch_stride, int per, int T_frames, int patches,
-                                                               int heads, int R, KvLayout lay, FastDiv div_patches) {
-  extern __shared__ float wl[];  // [2][heads][per] branch weights, then (POS) the positional embedding of this block's frames
+                                                               int heads, int R, KvLayout lay, FastDiv div_patches,
+                                                               const int32_t* __restrict__ frame_table, int store_frames) {
+  extern __shared__ float wl[];  // [2][heads][per] branch weights, then (POS) the positional embedding of this block's frames, then (TAB) T slots
   const HeadLanes ln(heads);
   const int hd = ln.hd;
   const int b = blockIdx.y;
@@ -47,6 +51,7 @@ __global__ __launch_bounds__(MAXT) void decoder_attn_map_kernel(const float* __r
   const int s_begin = blockIdx.x * per;  // < S: the grid has ceil(S / per) blocks per clip
   const int s_end = min(S, s_begin + per);
   float* const posl = wl + (size_t)2 * heads * per;
+  const int* const ftab = stage_slots<TAB, POS>(posl, frame_table, store_frames, b, T_frames, s_begin, s_end, S, D, div_patches);
   const int f0 = stage_pos<POS>(posl, lay.pos, s_begin, s_end, S, D, div_patches);
 
   float qs[8], qc[8];
@@ -57,14 +62,14 @@ __global__ __launch_bounds__(MAXT) void decoder_attn_map_kernel(const float* __r
     l = stats[((int64_t)b * heads + hd) * 2 + 1];
   }
 
-  const T* kb = ln.channels(k + (int64_t)b * T_frames * lay.frame_stride);
-  const KeySpan sp{s_end, S, D, f0, patches, R, lay, div_patches, frame_mask + (int64_t)b * T_frames, ln.channels(posl)};
+  const T* kb = ln.channels(k + (TAB ? 0 : (int64_t)b * T_frames * lay.frame_stride));
+  const KeySpan sp{s_end, S, D, f0, patches, R, lay, div_patches, frame_mask + (int64_t)b * T_frames, ln.channels(posl), ftab};
   float* const ws = wl + (size_t)hd * per;                  // softmax branch of my head
   float* const wc = wl + (size_t)(heads + hd) * per;        // CoDA branch
   for (int s0 = s_begin + ln.rs; s0 < s_end; s0 += UN * R) {
     Raw8<T> no_v[1];
     int po[UN];
-    const KeyRow me = key_trip<T, POS, false, false>(sp, ln, qs, qc, kb, kb, s0, no_v, po);
+    const KeyRow me = key_trip<T, POS, false, false, TAB>(sp, ln, qs, qc, kb, kb, s0, no_v, po);
     if (me.s < s_end) {
       float p;
       if (ext_w != nullptr) p = me.ok ? ext_w[((int64_t)b * heads + hd) * S + me.s] : 0.f;
@@ -88,15 +93,19 @@ __global__ __launch_bounds__(MAXT) void decoder_attn_map_kernel(const float* __r
 
 }  // namespace
 
-extern "C" int dfd_decoder_attn_map(const float* q, const void* k, int kv_dtype, const dfd_kv_layout_t* layout,
-                                    const uint8_t* frame_mask, const float* stats, const float* ext_weights, float* aff,
-                                    float* branches, int B, int T, int patches, int heads, int d, void* stream) {
-  if (int rc = check_decoder_attn("dfd_decoder_attn_map", q && k && aff && frame_mask && (stats || ext_weights), {k, q}, kv_dtype,
-                                  layout, B, T, patches, heads, d))
+namespace {
+
+// dfd_decoder_attn_map (frame_table == nullptr) and dfd_decoder_attn_map_frames: one check, one plan, the TAB flag apart
+int decoder_attn_map(const char* who, const float* q, const void* k, int kv_dtype, const dfd_kv_layout_t* layout,
+                     const uint8_t* frame_mask, const float* stats, const float* ext_weights, float* aff, float* branches, int B,
+                     int T, int patches, int heads, int d, const int32_t* frame_table, int store_frames, void* stream) {
+  const bool tab = frame_table != nullptr;
+  if (int rc = check_decoder_attn(who, q && k && aff && frame_mask && (stats || ext_weights), {k, q}, kv_dtype, layout, B, T, patches,
+                                  heads, d))
     return rc;
-  DFD_REQUIRE((int64_t)T * patches < (1ll << 30), "dfd_decoder_attn_map: bad shape");
+  DFD_REQUIRE((int64_t)T * patches < (1ll << 30), "%s: bad shape", who);
   DFD_REQUIRE((reinterpret_cast<uintptr_t>(aff) & 3) == 0 && (reinterpret_cast<uintptr_t>(branches) & 3) == 0,
-              "dfd_decoder_attn_map: aff and branches must be 4-byte aligned");
+              "%s: aff and branches must be 4-byte aligned", who);
   if (B == 0) return DFD_OK;
   const KvLayout lay = dfd_kv_layout(layout, patches, heads * HD);
   const FastDiv divp = FastDiv::make((uint32_t)patches);
@@ -111,17 +120,39 @@ extern "C" int dfd_decoder_attn_map(const float* q, const void* k, int kv_dtype,
   for (;; --trips) {
     per = UN * R * trips;
     const int span = lay.pos ? (per + patches - 2) / patches + 1 : 0;  // frames a block's rows can touch
-    lds = (size_t)2 * heads * per * sizeof(float) + (size_t)(span < T ? span : T) * heads * HD * sizeof(float);
+    lds = (size_t)2 * heads * per * sizeof(float) + (size_t)(span < T ? span : T) * heads * HD * sizeof(float) +
+          (tab ? (size_t)T * sizeof(int) : 0);  // the clip's staged slots
     if (trips == 1 || (lds <= 64 * 1024 && UN * R * (trips - 1) < S)) break;
   }
-  DFD_REQUIRE(lds <= 160 * 1024, "dfd_decoder_attn_map: %zu B of LDS", lds);
+  DFD_REQUIRE(lds <= 160 * 1024, "%s: %zu B of LDS", who, lds);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int64_t branch_stride = (int64_t)B * heads * S;
+  const Launch launch{dim3((S + per - 1) / per, B), dim3(blk.threads), lds, st};
   // the map's K loads are plain (no NT form)
   return decoder_attn_dispatch(kv_dtype, blk.threads, lay.pos != nullptr, false, [&](auto kt, auto mt, auto ps, auto) {
     using KT = typename decltype(kt)::type;
-    return launch_kernel("dfd_decoder_attn_map", decoder_attn_map_kernel<KT, decltype(mt)::value, decltype(ps)::value>,
-                         Launch{dim3((S + per - 1) / per, B), dim3(blk.threads), lds, st}, q, k, frame_mask, stats, ext_weights, aff,
-                         branches, branch_stride, per, T, patches, heads, R, lay, divp);
+    return pick(tab, [&](auto tb) {
+      return launch_kernel(who, decoder_attn_map_kernel<KT, decltype(mt)::value, decltype(ps)::value, decltype(tb)::value>, launch, q, k,
+                           frame_mask, stats, ext_weights, aff, branches, branch_stride, per, T, patches, heads, R, lay, divp,
+                           frame_table, store_frames);
+    });
   });
+}
+
+}  // namespace
+
+extern "C" int dfd_decoder_attn_map(const float* q, const void* k, int kv_dtype, const dfd_kv_layout_t* layout,
+                                    const uint8_t* frame_mask, const float* stats, const float* ext_weights, float* aff,
+                                    float* branches, int B, int T, int patches, int heads, int d, void* stream) {
+  return decoder_attn_map("dfd_decoder_attn_map", q, k, kv_dtype, layout, frame_mask, stats, ext_weights, aff, branches, B, T, patches,
+                          heads, d, nullptr, 0, stream);
+}
+
+extern "C" int dfd_decoder_attn_map_frames(const float* q, const void* k, int kv_dtype, const dfd_kv_layout_t* layout,
+                                           const uint8_t* frame_mask, const float* stats, const float* ext_weights, float* aff,
+                                           float* branches, int B, int T, int patches, int heads, int d, const int32_t* frame_table,
+                                           int store_frames, void* stream) {
+  if (int rc = check_frame_table("dfd_decoder_attn_map_frames", frame_table, store_frames)) return rc;
+  return decoder_attn_map("dfd_decoder_attn_map_frames", q, k, kv_dtype, layout, frame_mask, stats, ext_weights, aff, branches, B, T,
+                          patches, heads, d, frame_table, store_frames, stream);
 }

@@ -157,12 +157,16 @@ class Decoder(RuntimeStateMixin, nn.Module):
 
     # ---- plumbing ------------------------------------------------------------------------------
     def _unpack(self, kvs, m):
-        """-> (k_all, v_all, kv_pos, mask, B, T, P).  K/V come as the dense export [L, B*T*P, D] (positional embedding
+        """-> (k_all, v_all, kv_pos, mask, B, T, P, slots).  K/V come as the dense export [L, B*T*P, D] (positional embedding
         already added; kv_pos None), or IN PLACE: (k, v, pos) with k, v strided views [L, B*T, P, D] of the encoder's
-        q|k|v activations and pos [T, D] f32 (or None) added by the attention kernels as they read the rows."""
-        kv_pos = None
+        q|k|v activations and pos [T, D] f32 (or None) added by the attention kernels as they read the rows, or as a FRAME
+        STORE: (k_store, v_store, pos, slots) with k_store, v_store [L, C, P, D] and slots int32 [B*T] on the device, frame
+        t of clip b being frame slots[b*T + t] of the store (`capi.decoder_attn_fwd_frames`; slots is None otherwise)."""
+        kv_pos = slots = None
         if isinstance(kvs, list):
             k_all, v_all = self._pack(kvs)
+        elif len(kvs) == 4:
+            k_all, v_all, kv_pos, slots = kvs
         elif len(kvs) == 3:
             k_all, v_all, kv_pos = kvs
         else:
@@ -170,7 +174,11 @@ class Decoder(RuntimeStateMixin, nn.Module):
         if not k_all.is_cuda:
             raise capi.DfdError("the decoder runs on HIP kernels only: pass device tensors")
         B, T = m.shape
-        if k_all.dim() == 4:
+        if slots is not None:
+            assert k_all.dim() == 4 and v_all.shape == k_all.shape and v_all.stride() == k_all.stride(), "a frame store is [L, C, P, D]"
+            assert slots.is_cuda and slots.dtype == torch.int32 and tuple(slots.shape) == (B * T,), "slots: device int32 [B*T]"
+            P = k_all.shape[2]
+        elif k_all.dim() == 4:
             assert k_all.shape[1] == B * T and v_all.shape == k_all.shape and v_all.stride() == k_all.stride()
             P = k_all.shape[2]
         else:
@@ -179,7 +187,7 @@ class Decoder(RuntimeStateMixin, nn.Module):
             P = S // T
         assert k_all.shape[0] == len(self.layer_indices) and k_all.shape[-1] == self.width
         mask = m.to(device=k_all.device, dtype=torch.uint8).contiguous()
-        return k_all, v_all, kv_pos, mask, B, T, P
+        return k_all, v_all, kv_pos, mask, B, T, P, slots
 
     def _wt(self, name, w):
         """Transposed [K, N] copy of Linear weight `name`, refreshed when the parameter changed (its
@@ -251,13 +259,18 @@ class Decoder(RuntimeStateMixin, nn.Module):
             return None
         return capi.Dropout(drop_rng, site, self.dropout_p)
 
-    def run(self, kvs, m, drop_rng=None, attention=None):
+    def run(self, kvs, m, drop_rng=None, attention=None, slots_host=None):
         """-> (raw logits list, video_feature, normalised logits list).  With grad enabled and any
         trainable parameter, goes through `_DecoderFn` so `loss.backward()` reaches the parameters.
         `drop_rng`: this step's dropout state (device int64 {seed, step}) in train mode, None = no dropout.
         `attention`: a preallocated f32 [L, B, heads, T*P] tensor that receives, per block, the per-key weight
-        ½(softmax + CoDA) the block applied to its values (`capi.decoder_attn_map`); the no-grad path only."""
-        k_all, v_all, kv_pos, mask, B, T, P = self._unpack(kvs, m)
+        ½(softmax + CoDA) the block applied to its values (`capi.decoder_attn_map`); the no-grad path only.
+        `slots_host`: with the frame-store form of `kvs`, the host copy of its slots for the range check in front of the
+        launches; without it the device table is copied back once per call, which synchronises."""
+        k_all, v_all, kv_pos, mask, B, T, P, slots = self._unpack(kvs, m)
+        if slots is not None and self.attn_modes:
+            raise capi.DfdError("a frame table (k_store, v_store, pos, slots) with op_mode.attn_mode: the grouped-softmax pass scores "
+                                "its keys through dfd_decoder_rowdot, which reads no table; hand over the gathered rows")
         if attention is not None:
             want = (k_all.shape[0], B, self.heads, T * P)
             if attention.dtype != torch.float32 or tuple(attention.shape) != want or not attention.is_contiguous():
@@ -271,17 +284,22 @@ class Decoder(RuntimeStateMixin, nn.Module):
         if torch.is_grad_enabled() and (any(p.requires_grad for p in params) or k_all.requires_grad):
             if attention is not None:
                 raise NotImplementedError("attention maps come from the no-grad forward: call under torch.no_grad()")
+            if slots is not None:
+                raise capi.DfdError("a frame table (k_store, v_store, pos, slots) on the autograd path: the decoder's backward reads "
+                                    "no table; call under torch.no_grad(), or hand over the gathered rows")
             out = _DecoderFn.apply(self, k_all, v_all, mask, (B, T, P), names, (drop_rng, kv_pos), *params)
             n = len(self.out_dims)
             return list(out[1:1 + n]), out[0], list(out[1 + n:1 + 2 * n])
         w = {n: p.detach() for n, p in zip(names, params)}
         raws, feat, outs, _ = self._forward_kernels(w, k_all, v_all, mask, B, T, P, save=False, drop_rng=drop_rng, kv_pos=kv_pos,
-                                                    attention=attention)
+                                                    attention=attention, slots=slots, slots_host=slots_host)
         return raws, feat, outs
 
     # ---- forward on HIP kernels --------------------------------------------------------------
-    def _forward_kernels(self, w, k_all, v_all, mask, B, T, P, save, drop_rng=None, kv_pos=None, attention=None):
+    def _forward_kernels(self, w, k_all, v_all, mask, B, T, P, save, drop_rng=None, kv_pos=None, attention=None, slots=None,
+                         slots_host=None):
         assert attention is None or not save
+        assert slots is None or not (save or self.attn_modes), "a frame table: the no-grad forward without attn_mode only"
         dev = k_all.device
         D, H, L = self.width, self.heads, k_all.shape[0]
         f32 = dict(device=dev, dtype=torch.float32)
@@ -303,6 +321,8 @@ class Decoder(RuntimeStateMixin, nn.Module):
         xs = []  # per-block outputs, read by the per-layer heads of `global_prediction`
         mode_ws = None
         h, q, mix, stats, u = new(B, D), new(B, 2 * D), new(B, D), new(B, H, 2), new(B, 4 * D)
+        if slots is not None and slots_host is None:
+            slots_host = slots.cpu()  # one copy back for the range check of all L launches
         for i in range(L):
             pre = f"transformer.resblocks.{i}."
             if save:  # keep every intermediate of the block for the backward pass
@@ -334,9 +354,16 @@ class Decoder(RuntimeStateMixin, nn.Module):
                     if mode_ws is None:
                         mode_ws = (new(B, H, T * P), new(B, H, T * P))
                     aw = capi.decoder_attn_modes_fwd(q, k_all[i], mask, self.attn_modes, mode_ws[0], mode_ws[1], B, T, P, H, pos=kv_pos)
-                capi.decoder_attn_fwd(q, k_all[i], v_all[i], mask, mix, stats, ws, splits, B, T, P, H, ext_weights=aw, pos=kv_pos)
-                if attention is not None:  # the weights this call applied: same q, stats / aw and key layout
-                    capi.decoder_attn_map(q, k_all[i], mask, stats, attention[i], B, T, P, H, ext_weights=aw, pos=kv_pos)
+                if slots is not None:  # the store's layer read in place through the table
+                    capi.decoder_attn_fwd_frames(q, k_all[i], v_all[i], slots, mask, mix, stats, ws, splits, B, T, P, H, pos=kv_pos,
+                                                 table_host=slots_host)
+                    if attention is not None:
+                        capi.decoder_attn_map_frames(q, k_all[i], slots, mask, stats, attention[i], B, T, P, H, pos=kv_pos,
+                                                     table_host=slots_host)
+                else:
+                    capi.decoder_attn_fwd(q, k_all[i], v_all[i], mask, mix, stats, ws, splits, B, T, P, H, ext_weights=aw, pos=kv_pos)
+                    if attention is not None:  # the weights this call applied: same q, stats / aw and key layout
+                        capi.decoder_attn_map(q, k_all[i], mask, stats, attention[i], B, T, P, H, ext_weights=aw, pos=kv_pos)
                 lin(mix, pre + "attn.out_proj.", x, capi.EPI_BIAS_RESIDUAL)
                 capi.layernorm(x, g(pre + "ln_2.weight"), g(pre + "ln_2.bias"), h)
                 lin(h, pre + "mlp.c_fc.", u, capi.EPI_BIAS_QUICKGELU)

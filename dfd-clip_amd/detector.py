@@ -943,14 +943,18 @@ class Detector(RuntimeStateMixin, nn.Module):
         from . import stream
         return stream.push_frames(self, store, frames, valid)
 
-    def predict_windows(self, store, table, with_video_features=False):
+    def predict_windows(self, store, table, with_video_features=False, with_attention=False, gather="copy"):
         """`predict` for windows of stored frames: table [W, num_frames] absolute frame indices (`stream.window_table`); a
         frame that is evicted or not pushed yet raises by its index.  One `dfd_kv_move_frames` launch gathers the windows'
         raw rows into the store's dense [L, W*T, P, D] buffer, then exactly what `predict` does after the tower: the adapter
         where there is one, the decoder with this model's positional embedding, the stored `valid` flags as the mask.
-        No-grad inference in eval mode only.  Returns (task_logits, features) like `predict`."""
+        `gather="table"`: no gather launch and no dense buffer; the decoder reads the ring in place through the windows' slot
+        table (`capi.decoder_attn_fwd_frames`), bit for bit the same results.  A model with an adapter or `op_mode.attn_mode`
+        refuses it in words (`stream.choose_gather`); `gather="auto"` is "table" where it is allowed and "copy" elsewhere.
+        `with_attention`: features["attention"] as `predict` returns it, per tapped layer f32 [W, heads, T, patches], on either
+        arm.  No-grad inference in eval mode only.  Returns (task_logits, features) like `predict`."""
         from . import stream
-        return stream.predict_windows(self, store, table, with_video_features)
+        return stream.predict_windows(self, store, table, with_video_features, with_attention, gather)
 
     def _build_adapter(self, config, num_frames):
         """`adapter.type` none / normal (fresh) / pretrain (parameters from a checkpoint of a whole Detector, optionally

@@ -371,7 +371,7 @@ def infer_videos(model, videos, batch_size=30, modality="video", task_index=0, d
 
 @torch.no_grad()
 def infer_raw_video(model, frames, landmarks, aligner, batch_size=16, task_index=0, layout="hwc", swap_rb=False, with_logits=False,
-                    matrix=None, hop=None, tail="drop", encode_chunk=None):
+                    matrix=None, hop=None, tail="drop", encode_chunk=None, gather="copy"):
     """One decoded video to a verdict, as `pipeline.get_result` does after its file handling (`pipeline.py:328-351`), with
     the face alignment it reads from a pre-cropped file done here on the device (`align.FaceAligner`).
 
@@ -388,7 +388,9 @@ def infer_raw_video(model, frames, landmarks, aligner, batch_size=16, task_index
     frames, through a `stream.StreamingVerdict` fed with the crops in passes of `encode_chunk` frames (default
     `batch_size * num_frames`, the tower pass of the path above): every frame goes through the tower once, the K/V ring
     holds `num_frames + encode_chunk` frames whatever the length of the video, and "clips" above reads "windows".
-    `tail` is `stream.window_table`'s: "drop" as above, "last" adds the window that ends on the last frame.  Under
+    `tail` is `stream.window_table`'s: "drop" as above, "last" adds the window that ends on the last frame.  `gather` is
+    `StreamingVerdict`'s ("copy", "table" or "auto": whether the decoder reads a gathered copy of the windows' frames or the
+    ring in place; the same bits).  Under
     `precision="fp8"` the verdict depends on `encode_chunk` (`stream`'s note)."""
     model.eval()
     plan = aligner.plan(landmarks)
@@ -407,7 +409,7 @@ def infer_raw_video(model, frames, landmarks, aligner, batch_size=16, task_index
         raise ValueError(f"{crops.shape[0]} frames do not fill one clip of {T}")
     if hop is not None:
         chunk = int(encode_chunk) if encode_chunk is not None else batch_size * T
-        sv = StreamingVerdict(model, hop, encode_chunk=chunk, batch_size=batch_size, task_index=task_index, tail=tail)
+        sv = StreamingVerdict(model, hop, encode_chunk=chunk, batch_size=batch_size, task_index=task_index, tail=tail, gather=gather)
         for i in range(0, crops.shape[0], chunk):
             sv.push(crops[i:i + chunk], plan.valid[i:i + chunk])
         sv.flush()

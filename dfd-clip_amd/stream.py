@@ -6,12 +6,15 @@ frame goes through the tower ONCE (`Detector.push_frames`), its raw rows land in
 windows read them (`Detector.predict_windows`): one `dfd_kv_move_frames` launch gathers the frames of W windows into a dense
 [L, W*T, P, D] tensor, which the adapter and the decoder take exactly as `predict` hands them its own.  The decoder, the
 adapter and the encoder kernels are the ones `predict` runs; with overlap `T / hop` the tower, ~95 % of a forward, does
-`hop / T` of the work of re-encoding every window.
+`hop / T` of the work of re-encoding every window.  With `gather="table"` there is no gather and no dense tensor: the decoder
+reads the ring in place through the windows' slot table (`capi.decoder_attn_fwd_frames`), bit for bit the same verdicts.
 
   window_table      which frames each window names (pure host)
   FrameRing         the ring's bookkeeping: slots, eviction, validity (pure host)
   FrameStore        FrameRing + the device buffers
   move_reference    `capi.kv_move_frames` restated with torch indexing (the yardstick of the kernel's tests)
+  table_reference   the dense operand a slot table stands for (the yardstick of the tabled decoder attention's tests)
+  choose_gather     "copy" or "table" for a model (pure host)
   push_frames / predict_windows   what the two `Detector` methods run
   StreamingVerdict  frames in, (window start, logits) out: live feeds, and `harness.infer_raw_video(hop=)`
 
@@ -60,6 +63,44 @@ def move_reference(k, v, src_frame, dst_frame, k_out, v_out):
     k_out[:, d] = k[:, s]
     v_out[:, d] = v[:, s]
     return k_out, v_out
+
+
+def table_reference(k_layer, v_layer, slots):
+    """What `capi.decoder_attn_fwd_frames` / `decoder_attn_map_frames` read through a slot table, in plain torch on any device
+    (the yardstick of their tests): the rows `k_layer[slots.clamp(0, C - 1)]` of one store layer [C, P, D] (any strided
+    view) as the dense [B*T, P, D] operand of the untabled entry points; entries outside [0, C) are clamped as the kernel
+    clamps them.  `v_layer` may be None.  Returns (k, v)."""
+    idx = torch.as_tensor(slots).to(device=k_layer.device, dtype=torch.int64).reshape(-1).clamp(0, k_layer.shape[0] - 1)
+    return k_layer[idx].contiguous(), (None if v_layer is None else v_layer[idx].contiguous())
+
+
+GATHERS = ("copy", "table", "auto")
+
+
+def choose_gather(requested, has_adapter, attn_modes):
+    """How `predict_windows` hands a window batch to the decoder: "copy" (one `dfd_kv_move_frames` launch into the store's
+    dense buffer) or "table" (the decoder reads the ring in place through the slot table).  `requested`: "copy", "table", or
+    "auto" = "table" where it is allowed.  It is not allowed with an adapter (it needs the window's rows with the window's
+    positional embedding, as one dense operand) nor with `op_mode.attn_mode` (the grouped-softmax pass scores its keys
+    through a kernel that reads no table): "table" then raises `DfdError` naming the reason, "auto" is "copy"."""
+    if requested not in GATHERS:
+        raise ValueError(f"gather={requested!r}: 'copy', 'table' or 'auto'")
+    if requested == "copy":
+        return "copy"
+    reason = None
+    if has_adapter:
+        reason = "the model has an adapter, which needs the window's rows with the window's positional embedding as one dense tensor"
+    elif attn_modes:
+        reason = "op_mode.attn_mode scores the keys in a grouped-softmax pass that reads no frame table"
+    if reason is None:
+        return "table"
+    if requested == "table":
+        raise capi.DfdError(f"gather='table': {reason}; use gather='copy' or 'auto'")
+    return "copy"
+
+
+def _gather_for(model, requested):
+    return "copy" if requested == "copy" else choose_gather(requested, model.adapter is not None, model.decoder.attn_modes)
 
 
 class FrameRing:
@@ -189,9 +230,10 @@ def push_frames(model, store, frames, valid=None):
 
 
 @torch.no_grad()
-def predict_windows(model, store, table, with_video_features=False):
+def predict_windows(model, store, table, with_video_features=False, with_attention=False, gather="copy"):
     """`Detector.predict_windows`: see there."""
     _own(model, store)
+    gather = _gather_for(model, gather)
     if model.training:
         raise capi.DfdError("predict_windows is inference only (no dropout, no batch statistics): call model.eval() first")
     table = store.check(table)
@@ -202,19 +244,31 @@ def predict_windows(model, store, table, with_video_features=False):
     if W == 0:
         raise capi.DfdError("predict_windows: the table names no window")
     slots = store.slots(table).reshape(-1)
-    k4, v4 = store.dense(W * T)
-    capi.kv_move_frames(store.k, store.v, k4, v4, torch.from_numpy(slots).to(store.device), None, src_host=slots)
+    slots_dev = torch.from_numpy(slots).to(store.device)
     m = torch.from_numpy(store.mask(table)).to(store.device)
     pos = model.decoder.temporal_pos()
     model.decoder.use_graphs = False
-    if model.adapter is None:
-        kv = (k4, v4, pos)
+    if gather == "table":  # no gather launch, no dense buffer: the decoder reads the ring through the slots
+        kv = (store.k, store.v, pos, slots_dev)
     else:
-        model.adapter.use_graphs = False
-        rows = W * T * store.patches
-        kv = model.adapter.run(k4.view(store.layers, rows, store.width), v4.view(store.layers, rows, store.width), T, pos, None)
-    _, video_features, task_logits = model.decoder.run(kv, m, None)
-    return task_logits, ({"video": video_features} if with_video_features else {})
+        k4, v4 = store.dense(W * T)
+        capi.kv_move_frames(store.k, store.v, k4, v4, slots_dev, None, src_host=slots)
+        if model.adapter is None:
+            kv = (k4, v4, pos)
+        else:
+            model.adapter.use_graphs = False
+            rows = W * T * store.patches
+            kv = model.adapter.run(k4.view(store.layers, rows, store.width), v4.view(store.layers, rows, store.width), T, pos, None)
+    heads = model.encoder.heads
+    attention = torch.empty(store.layers, W, heads, T * store.patches, device=store.device, dtype=torch.float32) if with_attention else None
+    _, video_features, task_logits = model.decoder.run(kv, m, None, attention=attention,
+                                                       slots_host=torch.from_numpy(slots) if gather == "table" else None)
+    features = {}
+    if with_attention:
+        features["attention"] = [attention[i].view(W, heads, T, -1) for i in range(store.layers)]
+    if with_video_features:
+        features["video"] = video_features
+    return task_logits, features
 
 
 class StreamingVerdict:
@@ -235,9 +289,13 @@ class StreamingVerdict:
     staging and the dense buffer are ordered by it alone.  Call one object from one stream (and one thread); `push` returns
     after copying the new logits to the host, which waits for that stream.
 
+    `gather` is `predict_windows`'s: "copy" gathers every window batch into the store's dense buffer, "table" lets the
+    decoder read the ring in place (refused, in words, for a model with an adapter or an attn_mode), "auto" is "table" where
+    that is allowed.  The verdicts are the same bits either way.
+
     Under `precision="fp8"` the verdict depends on `encode_chunk` (see the module's note)."""
 
-    def __init__(self, model, hop, encode_chunk=None, capacity=None, batch_size=16, task_index=0, tail="drop"):
+    def __init__(self, model, hop, encode_chunk=None, capacity=None, batch_size=16, task_index=0, tail="drop", gather="copy"):
         self.hop = int(hop)
         self.T = int(model.num_frames)
         window_table(0, 0, self.T, self.hop, tail)  # its raises
@@ -245,6 +303,7 @@ class StreamingVerdict:
             raise ValueError(f"StreamingVerdict: batch_size={batch_size}")
         self.chunk = int(encode_chunk) if encode_chunk is not None else self.hop
         self.model, self.batch_size, self.task_index, self.tail = model, int(batch_size), int(task_index), tail
+        self.gather = _gather_for(model, gather)  # its raises, before any buffer
         self.store = FrameStore(model, int(capacity) if capacity is not None else self.T + self.chunk, self.chunk)
         self._pending, self._pending_valid, self._npending = [], [], 0
         self._next_start = 0
@@ -325,7 +384,7 @@ class StreamingVerdict:
         return out
 
     def _decode(self, table):
-        logits = self.model.predict_windows(self.store, table)[0][self.task_index].detach().to("cpu")
+        logits = self.model.predict_windows(self.store, table, gather=self.gather)[0][self.task_index].detach().to("cpu")
         new = [(int(table[i, 0]), logits[i]) for i in range(table.shape[0])]
         self._rows += new
         self._next_start = max(self._next_start, int(table[-1, 0]) + self.hop)

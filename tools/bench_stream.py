@@ -8,18 +8,28 @@ Setup: ViT-B/16, bf16, T = 30, layers 6..11 tapped (bench.py's model), no adapte
 
 (a) windows   hop 30 / 15 / 5 / 1.  "predict": per batch of 16 windows, `crops[table[i:i+16]]` is materialised and goes through
               `predict` (the tower re-encodes every frame T / hop times).  "store": a `StreamingVerdict` (encode_chunk 480 =
-              16 clips, batch 16) is fed the video and flushed.  Both copy each batch's logits to the host.  A series is one
-              video on the host clock between two device synchronisations; each arm is warmed with one video per hop, then
-              5 series per arm, alternating.  ms per video, windows/s, tower frames/s as median / min / max.
-(b) harness   `infer_raw_video(hop=None)` beside `hop=30` on 900 frames of 256 x 256 with landmarks (aligner crop 224): what one
-              extra K/V copy per frame costs against the path that stays the default.
+              16 clips, batch 16) is fed the video and flushed; every window batch is gathered into a dense buffer
+              (`gather="copy"`).  "table": the same with `gather="table"`: the decoder reads the ring in place through the slot
+              table.  All copy each batch's logits to the host.  A series is one video on the host clock between two device
+              synchronisations; each arm is warmed with one video per hop, then 5 series per arm, alternating.  ms per video,
+              windows/s, tower frames/s as median / min / max, and the peak of allocated device memory over the arm's
+              series (above what was allocated when the series began).  The yardstick of "table" is "store" of the same run.
+(b) harness   `infer_raw_video(hop=None)` beside `hop=30` and `hop=30, gather="table"` on 900 frames of 256 x 256 with landmarks
+              (aligner crop 224): what the K/V copies per frame cost against the path that stays the default.
 (c) kernel    `dfd_kv_move_frames` alone: ingest (480 frames, in-place q|k|v source -> ring slots, SRC_ONCE) and gather (W = 16
               windows, 480 frames, store -> dense): `--iters` launches between one HIP-event pair, 5 series; GB/s counts bytes
               read plus bytes written, against a device copy of as many bytes timed the same way in the same process.
+(c2) attention  one layer's decoder attention at W = 16 windows over the ring, hop 5 and hop 1: the tabled launch alone
+              (`decoder_attn_fwd_frames`) beside gather + untabled launch (`kv_move_frames` of that layer, then
+              `decoder_attn_fwd` on the dense rows), alternating; the launches walk round the six layers of the store, as the
+              decoder does, so that a layer is not re-read from cache by the next launch.  us per launch; GB/s of the bytes
+              NAMED (2 * W * T * P * D * 2: what the decoder reads) and of the bytes DISTINCT (the frames the 16 windows share,
+              once), for both arms.
 (d) live      hop 1 / 5 / 30 with encode_chunk = hop on a warm ring: ms on the host clock from `push(hop frames)` to the
-              logits on the host (push returns them), median / min / max over `--live` pushes.
+              logits on the host (push returns them), median / min / max over `--live` pushes, for `gather="copy"` and "table".
 
-Nothing is asserted but that both arms of (a) and (b) give the same number of windows.
+Nothing is asserted but that the arms of (a) and (b) give the same number of windows, and that "store" and "table" give the same
+bits.
 
 usage: python tools/bench_stream.py [--frames 900] [--repeats 5] [--iters 20] [--live 30] [--hops 30,15,5,1] [--out PATH]
 """
@@ -76,30 +86,39 @@ def windows_leg(det, crops, hops, repeats):
                 rows.append(det.predict(x, ones[:x.shape[0]])[0][0].detach().to("cpu"))
         return torch.cat(rows)
 
-    def by_store(hop):
-        sv = StreamingVerdict(det, hop, encode_chunk=BATCH * T, batch_size=BATCH)
+    def by_store(hop, gather="copy"):
+        sv = StreamingVerdict(det, hop, encode_chunk=BATCH * T, batch_size=BATCH, gather=gather)
         sv.push(crops)
         sv.flush()
         return sv.result(with_logits=True)[2]
 
     out = {}
     for hop in hops:
-        arms = {"predict": by_predict, "store": by_store}
+        arms = {"predict": by_predict, "store": by_store, "table": lambda h: by_store(h, "table")}
         first = {n: timed(lambda: fn(hop)) for n, fn in arms.items()}
         W = first["predict"][1].shape[0]
-        assert first["store"][1].shape[0] == W
+        assert first["store"][1].shape[0] == W and torch.equal(first["store"][1], first["table"][1])
         gap = (first["predict"][1].double() - first["store"][1].double()).abs().max().item()
-        ms = {n: [] for n in arms}
+        ms, peak = {n: [] for n in arms}, {n: 0 for n in arms}
         for _ in range(repeats):
             for n, fn in arms.items():
+                torch.cuda.synchronize()
+                base = torch.cuda.memory_allocated()
+                torch.cuda.reset_peak_memory_stats()
                 ms[n].append(timed(lambda: fn(hop))[0])
+                peak[n] = max(peak[n], torch.cuda.max_memory_allocated() - base)
                 print(f"  hop {hop} {n}: {ms[n][-1]:.1f} ms", file=sys.stderr, flush=True)
-        tower = {"predict": W * T, "store": (W - 1) * hop + T}
-        leg = {"windows": W, "warm_ms": {n: round(first[n][0], 1) for n in arms}, "max_logit_gap_between_arms": gap}
+        tower = {"predict": W * T, "store": (W - 1) * hop + T, "table": (W - 1) * hop + T}
+        leg = {"windows": W, "warm_ms": {n: round(first[n][0], 1) for n in arms}, "max_logit_gap_between_arms": gap,
+               "table_bits_equal_store": True}
         for n in arms:
-            leg[n] = {"ms_per_video": spread(ms[n], 2), "windows_per_s": spread([W * 1e3 / t for t in ms[n]], 1),
-                      "tower_frames": tower[n], "tower_frames_per_s": spread([tower[n] * 1e3 / t for t in ms[n]], 0)}
+            leg[n] = {"ms_per_video": spread(ms[n], 2), "series_ms": [round(t, 2) for t in ms[n]],
+                      "windows_per_s": spread([W * 1e3 / t for t in ms[n]], 1),
+                      "tower_frames": tower[n], "tower_frames_per_s": spread([tower[n] * 1e3 / t for t in ms[n]], 0),
+                      "peak_allocated_mb_above_start": round(peak[n] / 2**20, 1)}
         leg["store_over_predict"] = round(statistics.median(ms["store"]) / statistics.median(ms["predict"]), 4)
+        leg["table_over_predict"] = round(statistics.median(ms["table"]) / statistics.median(ms["predict"]), 4)
+        leg["table_over_store"] = round(statistics.median(ms["table"]) / statistics.median(ms["store"]), 4)
         out[f"hop_{hop}"] = leg
     return out
 
@@ -113,9 +132,10 @@ def harness_leg(det, F, repeats, device):
     aligner = AL.FaceAligner(ref, canvas=256, crop=224, border=0)
     frames = torch.randint(0, 256, (F, 256, 256, 3), dtype=torch.uint8, device=device, generator=torch.Generator(device=device).manual_seed(5))
     arms = {"hop_none": lambda: infer_raw_video(det, frames, lm, aligner, batch_size=BATCH, with_logits=True)[2],
-            "hop_30": lambda: infer_raw_video(det, frames, lm, aligner, batch_size=BATCH, with_logits=True, hop=T)[2]}
+            "hop_30": lambda: infer_raw_video(det, frames, lm, aligner, batch_size=BATCH, with_logits=True, hop=T)[2],
+            "hop_30_table": lambda: infer_raw_video(det, frames, lm, aligner, batch_size=BATCH, with_logits=True, hop=T, gather="table")[2]}
     first = {n: timed(fn) for n, fn in arms.items()}
-    assert first["hop_none"][1].shape == first["hop_30"][1].shape
+    assert first["hop_none"][1].shape == first["hop_30"][1].shape and torch.equal(first["hop_30"][1], first["hop_30_table"][1])
     ms = {n: [] for n in arms}
     for _ in range(repeats):
         for n, fn in arms.items():
@@ -125,6 +145,8 @@ def harness_leg(det, F, repeats, device):
     for n in arms:
         out[n] = {"ms_per_video": spread(ms[n], 2), "series_ms": [round(t, 2) for t in ms[n]]}
     out["hop_30_over_hop_none"] = round(statistics.median(ms["hop_30"]) / statistics.median(ms["hop_none"]), 4)
+    out["hop_30_table_over_hop_none"] = round(statistics.median(ms["hop_30_table"]) / statistics.median(ms["hop_none"]), 4)
+    out["hop_30_table_over_hop_30"] = round(statistics.median(ms["hop_30_table"]) / statistics.median(ms["hop_30"]), 4)
     return out
 
 
@@ -173,24 +195,98 @@ def kernel_leg(iters, repeats, device):
     return out
 
 
+def attention_leg(iters, repeats, device):
+    """(c2): one layer's tabled launch beside gather + untabled launch, W = 16 windows, walking round the store's layers"""
+    from dfd_clip_amd import capi
+    L, P, D, H, W = len(LAYERS), 196, 768, 12, BATCH
+    S, cap = T * P, BATCH * T + T
+    sk, sv = (torch.empty(L, cap, P, D, device=device, dtype=torch.bfloat16).normal_() for _ in range(2))
+    dk, dv = (torch.empty(L, W * T, P, D, device=device, dtype=torch.bfloat16) for _ in range(2))
+    q = torch.randn(W, 2 * D, device=device)
+    pos = torch.randn(T, D, device=device) * 0.02
+    m = torch.ones(W, T, dtype=torch.uint8, device=device)
+    splits = max(1, min(S // 64, max(1, 768 // W)))  # Decoder._splits
+    ws = torch.empty(capi.decoder_attn_workspace_bytes(W, H, 64, splits) // 4, device=device)
+    mix, stats = torch.empty(W, D, device=device), torch.empty(W, H, 2, device=device)
+    out = {"windows": W, "layers_walked": L, "splits": splits, "named_bytes": 2 * W * T * P * D * 2}
+    for hop in (5, 1):
+        wins = torch.as_tensor([(cap - 11 + w * hop + j) % cap for w in range(W) for j in range(T)], dtype=torch.int32)  # a wrap
+        dwins = wins.to(device)
+        distinct = len(set(wins.tolist()))
+        layer = [0]
+
+        def tabled():
+            i = layer[0] = (layer[0] + 1) % L
+            capi.decoder_attn_fwd_frames(q, sk[i], sv[i], dwins, m, mix, stats, ws, splits, W, T, P, H, pos=pos, table_host=wins)
+
+        def gathered():
+            i = layer[0] = (layer[0] + 1) % L
+            capi.kv_move_frames(sk[i:i + 1], sv[i:i + 1], dk[i:i + 1], dv[i:i + 1], dwins, None, src_host=wins)
+            capi.decoder_attn_fwd(q, dk[i], dv[i], m, mix, stats, ws, splits, W, T, P, H, pos=pos)
+
+        def untabled_alone():
+            i = layer[0] = (layer[0] + 1) % L
+            capi.decoder_attn_fwd(q, dk[i], dv[i], m, mix, stats, ws, splits, W, T, P, H, pos=pos)
+
+        calls = {"table": tabled, "gather_plus_untabled": gathered, "untabled_alone": untabled_alone}
+
+        def series(fn):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                fn()
+            e1.record()
+            e1.synchronize()
+            return e0.elapsed_time(e1) * 1e3 / iters
+
+        for fn in calls.values():
+            for _ in range(L):
+                fn()
+        gathered()
+        ref = mix.clone()
+        layer[0] -= 1  # the same layer again
+        tabled()
+        assert torch.isfinite(mix).all() and torch.equal(ref, mix)  # (synchronises)
+        us = {n: [] for n in calls}
+        for _ in range(repeats):
+            for n, fn in calls.items():
+                us[n].append(series(fn))
+        named, dist = out["named_bytes"], 2 * distinct * P * D * 2
+        leg = {"distinct_frames": distinct, "named_frames": W * T, "distinct_bytes": dist}
+        for n in calls:
+            med = statistics.median(us[n])
+            leg[n] = {"us": spread(us[n], 2), "named_gbs": round(named / med / 1e3, 1), "distinct_gbs": round(dist / med / 1e3, 1)}
+        leg["table_over_gather_plus_untabled"] = round(statistics.median(us["table"]) / statistics.median(us["gather_plus_untabled"]), 4)
+        leg["table_over_untabled_alone"] = round(statistics.median(us["table"]) / statistics.median(us["untabled_alone"]), 4)
+        out[f"hop_{hop}"] = leg
+    return out
+
+
 def live_leg(det, crops, pushes):
     from dfd_clip_amd.stream import StreamingVerdict
     out = {}
     for hop in (1, 5, 30):
-        sv = StreamingVerdict(det, hop)
+        leg = {}
+        svs = {g: StreamingVerdict(det, hop, gather=g) for g in ("copy", "table")}
         at = 0
-        for _ in range(T // hop + 4):  # fill the ring and warm every shape: from here each push completes one window
-            sv.push(crops[at:at + hop])
+        for _ in range(T // hop + 4):  # fill the rings and warm every shape: from here each push completes one window
+            for sv in svs.values():
+                sv.push(crops[at:at + hop])
             at += hop
-        ms = []
+        ms = {g: [] for g in svs}
         for _ in range(pushes):
             if at + hop > crops.shape[0]:
                 at = 0  # (the content of a frame does not change its cost)
-            t, got = timed(lambda: sv.push(crops[at:at + hop]))
-            assert len(got) == 1
-            ms.append(t)
+            for g, sv in svs.items():  # alternating
+                t, got = timed(lambda: sv.push(crops[at:at + hop]))
+                assert len(got) == 1
+                ms[g].append(t)
             at += hop
-        out[f"hop_{hop}"] = {"ms_push_to_verdict": spread(ms, 3), "pushes": pushes, "ring_frames": sv.store.capacity}
+        for g in svs:
+            leg[g] = {"ms_push_to_verdict": spread(ms[g], 3)}
+        leg.update(pushes=pushes, ring_frames=svs["copy"].store.capacity,
+                   table_over_copy=round(statistics.median(ms["table"]) / statistics.median(ms["copy"]), 4))
+        out[f"hop_{hop}"] = leg
     return out
 
 
@@ -216,6 +312,7 @@ def main():
     out["windows"] = windows_leg(det, crops, [int(h) for h in args.hops.split(",")], args.repeats)
     out["harness"] = harness_leg(det, args.frames, args.repeats, device)
     out["kernel"] = kernel_leg(args.iters, args.repeats, device)
+    out["attention"] = attention_leg(5 * args.iters, args.repeats, device)  # (a launch is ~0.1 ms: five times the launches per series)
     out["live"] = live_leg(det, crops, args.live)
     line = json.dumps(out)
     print(line)
